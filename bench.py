@@ -9,19 +9,27 @@ Default workload = **TPC-H Q3 SF10** — the configuration BASELINE.json's
 metric is quoted on; it fits one GPU (~2.3 GB), so it is the N=1 headline
 (VERDICT r1 #1). The query text is the REAL Q3 ('BUILDING',
 DATE '1995-03-15'); tables are registered with their real types
-(dictionary-encoded mktsegment, DATE columns). At N=1 the default run also
-reports the C2 scan workload (BASELINE configs[1]) in the same JSON line
-under "secondary".
+(dictionary-encoded mktsegment, DATE columns).
+
+A plain run does only what the headline figure needs: generate + upload,
+warm up, time K steps, print ONE JSON line (rank 0) with the contract
+fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...). `--dump-outputs DIR` additionally writes the result of
+the last timed step (the frame `Context.sql(...).compute()` returns) as
+`DIR/<NN>_<column>.npy`, float64; inputs are seeded, so two builds can be
+compared output for output.
+
+`--full` adds everything else to the same JSON line: a separate profiled
+pass (`roofline`, `kernels`), `cpu_baseline` (the oracle timed on host cores
+on a bounded sample — reported baseline, not the target) and, at N=1 on the
+default workload, the C2 scan workload (BASELINE configs[1]) under
+"secondary".
 
 Roofline accounting: `roofline.frac` = whole-op
 algorithmic bytes ÷ whole-op kernel time — the summed HIP-event time of
 EVERY kernel a step launches, not the per-launch time of one family.
 The dominant family's own per-launch numbers are reported under
 `roofline.dominant` for kernel-level comparison against rocprof.
-
-Rank 0 prints ONE JSON line with the contract fields + roofline +
-cpu_baseline (the oracle timed on host cores on a bounded sample —
-reported baseline, not the target).
 """
 import argparse
 import json
@@ -248,10 +256,77 @@ def _oracle_c2_chunk(key, val):
     return oracle_c1_c2_groupby(key, val, predicate=True)
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this
+DUMP_SAMPLE_SEED = 1234
+
+
+def _as_float64(series):
+    """One result column as float64: numbers as they are, dates/timestamps
+    as ns since the epoch, strings as their rank among the column's sorted
+    distinct values; NULL → NaN."""
+    import pandas as pd
+
+    arr = series.to_numpy()
+    if np.issubdtype(arr.dtype, np.datetime64):
+        ns = arr.astype("datetime64[ns]")
+        out = ns.astype(np.int64).astype(np.float64)
+        out[np.isnat(ns)] = np.nan
+        return out
+    if arr.dtype == object:
+        null = pd.isna(series).to_numpy()
+        out = np.full(len(arr), np.nan)
+        if (~null).any():
+            _, inv = np.unique(arr[~null].astype(str), return_inverse=True)
+            out[~null] = inv
+        return out
+    return pd.to_numeric(series, errors="coerce").to_numpy(
+        dtype=np.float64, na_value=np.nan)
+
+
+def dump_outputs(result, workload, out_dir):
+    """Write what the last timed step handed back — the frame a caller of
+    the timed path receives — one float64 `<NN>_<column>.npy` per column.
+    Queries without ORDER BY return rows in no fixed order, so their rows
+    are sorted by all columns first; a result above the size budget is cut
+    to a fixed seeded row sample (same rows for every build)."""
+    import re
+
+    import pandas as pd
+
+    if hasattr(result, "compute"):
+        pdf = result.compute()
+    elif isinstance(result, pd.DataFrame):
+        pdf = result
+    else:  # (key, [values]) device columns of the distributed merge
+        mkey, mvals = result
+        pdf = pd.DataFrame({"key": mkey.to_numpy()[0]})
+        for i, v in enumerate(mvals):
+            pdf[f"val{i}"] = v.to_numpy()[0]
+    cols = {f"{i:02d}_" + re.sub(r"[^A-Za-z0-9_.-]", "_", str(name)):
+            _as_float64(pdf.iloc[:, i]) for i, name in enumerate(pdf.columns)}
+    n = len(pdf)
+    names = list(cols)
+    if n and "ORDER BY" not in WORKLOADS[workload]["sql"].upper():
+        order = np.lexsort([cols[k] for k in reversed(names)])
+        cols = {k: v[order] for k, v in cols.items()}
+    cap = DUMP_BUDGET_BYTES // (8 * max(1, len(names)))
+    if n > cap:
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+            n, size=cap, replace=False))
+        cols = {k: v[keep] for k, v in cols.items()}
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, v in cols.items():
+        np.save(out_dir / f"{k}.npy", np.ascontiguousarray(v))
+    log(f"[bench] wrote {len(names)} output columns "
+        f"({min(n, cap)} of {n} rows) under {out_dir}")
+
+
 def run_workload(workload, args, world, rank, local_rank, pg,
-                 with_cpu_baseline):
+                 with_cpu_baseline, full, dump_dir=None):
     """Generate + upload, warm up, time K steps; return the metrics dict
-    (rank 0) or None."""
+    (rank 0) or None. `full` adds the profiled pass (roofline + per-kernel
+    figures) and, with `with_cpu_baseline`, the CPU baseline leg."""
     import torch
 
     w = WORKLOADS[workload]
@@ -272,9 +347,11 @@ def run_workload(workload, args, world, rank, local_rank, pg,
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run_step(c, workload, world, pg)
+        last = None  # release the previous step's result before the next
+        last = run_step(c, workload, world, pg)
     runtime.synchronize()
     if torch.cuda.is_available():
         torch.cuda.synchronize(local_rank)
@@ -288,6 +365,37 @@ def run_workload(workload, args, world, rank, local_rank, pg,
                          device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(last, workload, dump_dir)
+    last = None
+
+    ms_per_step = elapsed * 1000.0 / args.steps
+    total_rows = rows_per_rank * world
+    value = total_rows * args.steps / elapsed
+    result = {
+        "metric": "rows/s",
+        "value": round(value, 1),
+        "unit": "rows/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": w["scaling"],
+        "vs_baseline": None,  # BASELINE.md: reference publishes no numbers
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": workload,
+            "rows_per_gpu": rows_per_rank,
+            "n_groups": w.get("n_groups"),
+            "sql": " ".join(w["sql"].split())[:160],
+            "parallelism": f"dp{world}" if world > 1 else "single",
+        },
+    }
+    if not full:
+        return result if rank == 0 else None
+
     # profiled pass (same step count → same per-step kernel accounting)
     runtime.prof_enable(True)
     runtime.prof_reset()
@@ -301,10 +409,6 @@ def run_workload(workload, args, world, rank, local_rank, pg,
 
     if rank != 0:
         return None
-
-    ms_per_step = elapsed * 1000.0 / args.steps
-    total_rows = rows_per_rank * world
-    value = total_rows * args.steps / elapsed
 
     # Whole-op roofline: algorithmic bytes of one step ÷ the summed
     # HIP-event time of EVERY kernel that step launched (VERDICT r1 weak#4:
@@ -347,32 +451,14 @@ def run_workload(workload, args, world, rank, local_rank, pg,
         log("[bench] timing CPU baseline (oracle restatement)")
         cpu_baseline = cpu_baseline_leg(workload)
 
-    return {
-        "metric": "rows/s",
-        "value": round(value, 1),
-        "unit": "rows/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": w["scaling"],
-        "vs_baseline": None,  # BASELINE.md: reference publishes no numbers
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": workload,
-            "rows_per_gpu": rows_per_rank,
-            "n_groups": w.get("n_groups"),
-            "sql": " ".join(w["sql"].split())[:160],
-            "parallelism": f"dp{world}" if world > 1 else "single",
-        },
+    result.update({
         "roofline": roofline,
         "cpu_baseline": cpu_baseline,
         "kernels": {k: {"ms_per_launch": round(v["ms"] / v["launches"], 4),
                         "launches": v["launches"]}
                     for k, v in sorted(prof.items())},
-    }
+    })
+    return result
 
 
 def main():
@@ -382,9 +468,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="q3_sf10",
                     help="headline default: TPC-H Q3 SF10 (BASELINE metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the profiled pass (roofline + per-kernel "
+                         "figures), the CPU baseline and, at N=1 on the "
+                         "default workload, the C2 secondary workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's result "
+                         "columns as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the C2 secondary line at N=1")
+                    help="with --full: skip the C2 secondary line at N=1")
     args = ap.parse_args()
 
     import torch
@@ -403,17 +497,17 @@ def main():
         dist.init_process_group(backend="nccl")
         pg = dist.group.WORLD
 
-    with_cpu = world == 1 and not args.no_cpu_baseline
+    with_cpu = args.full and world == 1 and not args.no_cpu_baseline
     out = run_workload(args.workload, args, world, rank, local_rank, pg,
-                       with_cpu)
+                       with_cpu, args.full, args.dump_outputs)
 
-    # At N=1 the default run also measures the C2 scan workload
-    # (BASELINE configs[1] — the single-GPU north-star kernel) and attaches
-    # it to the same JSON line (driver contract: ONE line on stdout).
-    if (world == 1 and args.workload == "q3_sf10"
+    # At N=1 a --full run of the default workload also measures the C2 scan
+    # workload (BASELINE configs[1] — the single-GPU north-star kernel) and
+    # attaches it to the same JSON line (driver contract: ONE line on stdout).
+    if (args.full and world == 1 and args.workload == "q3_sf10"
             and not args.no_secondary):
         sec = run_workload("c2_filter_groupby_100m", args, world, rank,
-                           local_rank, pg, with_cpu)
+                           local_rank, pg, with_cpu, True)
         if out is not None and sec is not None:
             out["secondary"] = {
                 "workload": "c2_filter_groupby_100m",

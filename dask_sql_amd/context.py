@@ -288,6 +288,7 @@ class Context:
         self._runtime = None
         self._device_id = device_id
         self._plan_cache: dict = {}
+        self._agg_memo = None  # per-query Aggregate results (convert.py)
         self._schema_version = 0
 
     # -- reference context.py:168 create_table ----------------------------
@@ -596,7 +597,13 @@ class Context:
             return res
         rel = self._get_ral(sql)
         logger.debug("plan:\n%s", rel.explain())
-        dc = RelConverter.convert(rel, context=self)
+        outer = self._agg_memo
+        if outer is None:
+            self._agg_memo = {}  # lives for this query only
+        try:
+            dc = RelConverter.convert(rel, context=self)
+        finally:
+            self._agg_memo = outer
         res = ResultFrame(dc, rel, self)
         return res.compute() if not return_futures else res
 

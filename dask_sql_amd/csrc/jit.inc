@@ -90,6 +90,8 @@ __device__ __forceinline__ i64 jit_day(i64 v) {
 )";
 
 // ---- expression → C source ------------------------------------------------
+static const size_t JIT_EXPR_MAX_CHARS = 1 << 16;
+
 struct JitExprGen {
   const ColsArg* cols;  // metadata only (dtype + validity presence)
   bool ok = true;
@@ -216,6 +218,10 @@ struct JitExprGen {
           break;
         case DSX_OP_AND:
           pop2(a, av, ka, b, bv, kb);
+          if (av == "true" && bv == "true") {  // no NULLs: plain &&
+            push("(i64)((" + a + ") && (" + b + "))", "true", 'l');
+            break;
+          }
           // SQL 3VL: F if either valid-false; else NULL if any NULL
           push("(i64)(((" + av + ") && !(" + a + ")) || ((" + bv +
                    ") && !(" + b + ")) ? 0 : 1)",
@@ -225,6 +231,10 @@ struct JitExprGen {
           break;
         case DSX_OP_OR:
           pop2(a, av, ka, b, bv, kb);
+          if (av == "true" && bv == "true") {  // no NULLs: plain ||
+            push("(i64)((" + a + ") || (" + b + "))", "true", 'l');
+            break;
+          }
           push("(i64)((((" + av + ") && (" + a + ")) || ((" + bv + ") && (" +
                    b + "))) ? 1 : 0)",
                "((((" + av + ") && (" + a + ")) || ((" + bv + ") && (" + b +
@@ -326,6 +336,12 @@ struct JitExprGen {
         default:
           ok = false;
       }
+      // the 3VL AND/OR forms repeat their operands' text, so a long chain
+      // over nullable columns grows ~2.6x per level: past this size leave
+      // the expression to the interpreter kernels
+      if (!stk.empty() &&
+          stk.back()[0].size() + stk.back()[1].size() > JIT_EXPR_MAX_CHARS)
+        ok = false;
     }
     return ok && stk.size() == 1;
   }

@@ -37,7 +37,32 @@ class RelConverter:
         logger.debug(
             f"Processing REL {node_type} using {plugin_instance.__class__.__name__}"
         )
-        return plugin_instance.convert(rel, context=context)
+        # Within one query, structurally equal Aggregate subtrees (a CTE or
+        # view referenced twice) run once and share their result: float
+        # SUMs accumulate in no fixed order, so a second run could differ
+        # in the last bits and break `x = (SELECT MAX(x) FROM cte)`.
+        memo = getattr(context, "_agg_memo", None)
+        if memo is None or node_type != "Aggregate":
+            return plugin_instance.convert(rel, context=context)
+        key = rel.signature()
+        if key not in memo:
+            memo[key] = plugin_instance.convert(rel, context=context)
+        return memo[key]
+
+
+def _host_to_device(dc, context):
+    """Re-upload a HostDataContainer (row order kept) as a DataContainer."""
+    from dask_sql_amd.datacontainer import (ColumnContainer, DataContainer,
+                                            HostDataContainer)
+    if not isinstance(dc, HostDataContainer):
+        return dc
+    from dask_sql_amd.context import RegisteredTable, _from_pandas
+    names = [str(c) for c in dc.pdf.columns]
+    backend = [f"h{i}__{n}" for i, n in enumerate(names)]
+    pdf = dc.pdf.set_axis(backend, axis=1).reset_index(drop=True)
+    table = RegisteredTable(_from_pandas(pdf)).upload(context._get_runtime())
+    return DataContainer(table, ColumnContainer(names,
+                                                dict(zip(names, backend))))
 
 
 class BaseRelPlugin:
@@ -49,11 +74,17 @@ class BaseRelPlugin:
         raise NotImplementedError
 
     @staticmethod
-    def assert_inputs(rel, n=1, context=None):
-        # reference rel/base.py:67-86: depth-first recursion over inputs
+    def assert_inputs(rel, n=1, context=None, host_ok=False):
+        # reference rel/base.py:67-86: depth-first recursion over inputs.
+        # A Sort/Limit below (derived table, hidden ORDER BY column) hands
+        # back a host frame; only plugins that say host_ok take it as is,
+        # every other one gets it back as device columns.
         input_rels = rel.get_inputs()
         assert len(input_rels) == n, (len(input_rels), n)
-        return [RelConverter.convert(r, context) for r in input_rels]
+        dcs = [RelConverter.convert(r, context) for r in input_rels]
+        if not host_ok:
+            dcs = [_host_to_device(dc, context) for dc in dcs]
+        return dcs
 
     @staticmethod
     def fix_column_to_row_type(cc, row_type):

@@ -29,6 +29,23 @@ def _dicts_of(cols):
     return [getattr(c, "dictionary", None) for c in cols]
 
 
+def _codes_i32(runtime, col):
+    """Dictionary codes as a 4-byte column, the width a gather reads its
+    row ids in. Factorized table columns already are. Other widths (8-byte
+    codes out of a groupby — DISTINCT, GROUP BY keys — or 1-byte codes of a
+    declared dictionary) used to be read as if they were 4 bytes wide; the
+    VM has no 4-byte output, so they are converted through the host."""
+    if col.dtype == rt.I32:
+        return col
+    arr, valid = col.to_numpy()
+    arr = np.array(arr, dtype=np.int32)
+    if valid is not None:
+        arr[~valid.astype(bool)] = 0  # NULL rows: any in-range code
+    return runtime.upload_column(
+        arr,
+        None if valid is None else valid.astype(np.uint8), rt.I32)
+
+
 def _minmax_cached(runtime, col):
     """Column statistics memo (the reference caches table statistics too —
     datacontainer.py Statistics / statistics.py:21). Derived columns (gather
@@ -425,6 +442,10 @@ class DaskJoinPlugin(BaseRelPlugin):
         out_idx = join.output_indices if getattr(join, "output_indices",
                                                  None) is not None \
             else list(range(len(combined)))
+        if (getattr(join, "output_indices", None) is None
+                and str(join.getJoinType()) == "LEFTSEMI"):
+            # unpruned SEMI join (e.g. below a UNION): lhs columns only
+            out_idx = list(range(n_lhs_cols))
         from dask_sql_amd.planner.prune import _expr_refs, _remap
 
         # FUSED PATH: emit writes the output columns directly — no pair
@@ -637,11 +658,12 @@ class DaskJoinPlugin(BaseRelPlugin):
             miss = len(dl)  # sentinel: never present on the lhs side
             m = np.array([index.get(s, miss) for s in dr], dtype=np.int64)
             map_col = runtime.upload_column(m)
-            g = runtime.gather(map_col, rcols[ri].data,
+            codes = _codes_i32(runtime, rcols[ri])
+            g = runtime.gather(map_col, codes.data,
                                dc_rhs.table.num_rows)
             rem = rt.DeviceColumn(runtime, g.data, rcols[ri].validity,
                                   g.len, rt.I64, owner=False,
-                                  keep_alive=(g, rcols[ri], map_col))
+                                  keep_alive=(g, rcols[ri], map_col, codes))
             rem.dictionary = dl
             sub[ri] = rem
         if not sub:
@@ -719,10 +741,12 @@ class DaskJoinPlugin(BaseRelPlugin):
         finally:
             runtime.hash_table_free(table)
         keep = (fid, lcol, rcol)
+        # fid holds the scattered build positions: 4-byte ids like bsel
+        assert fid.dtype == rt.I32, fid.dtype
         lid = rt.DeviceColumn(runtime, fid.data, lcol.validity, n_l,
-                              rt.I64, owner=False, keep_alive=keep)
-        rid = rt.DeviceColumn(runtime, fid.data + 8 * n_l, rcol.validity,
-                              n_r, rt.I64, owner=False, keep_alive=keep)
+                              rt.I32, owner=False, keep_alive=keep)
+        rid = rt.DeviceColumn(runtime, fid.data + 4 * n_l, rcol.validity,
+                              n_r, rt.I32, owner=False, keep_alive=keep)
         return lid, rid, G
 
     def _equi_join(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on, join_type,
@@ -1161,10 +1185,20 @@ class DaskAggregatePlugin(BaseRelPlugin):
                     if s.notna().any() else None)
             return f
 
+        def _strsafe(how):
+            # string columns with NULLs: pandas' object min/max compares
+            # None against str — reduce over the non-NULL values instead
+            def f(sg):
+                if sg.obj.dtype == object:
+                    return sg.agg(lambda s: getattr(s.dropna(), how)()
+                                  if s.notna().any() else None)
+                return getattr(sg, how)()
+            return f
+
         builtin = {"sum": lambda sg: sg.sum(min_count=1),
                    "count": lambda sg: sg.count(),
                    "avg": lambda sg: sg.mean(),
-                   "min": lambda sg: sg.min(), "max": lambda sg: sg.max(),
+                   "min": _strsafe("min"), "max": _strsafe("max"),
                    "bit_and": _bitred(np.bitwise_and),
                    "bit_or": _bitred(np.bitwise_or),
                    "bit_xor": _bitred(np.bitwise_xor),
@@ -1296,8 +1330,11 @@ class DaskAggregatePlugin(BaseRelPlugin):
         # key specs from minmax (float key: bit-pattern mode, single key;
         # floats inside composite key sets are densified to integer ids)
         name_idx = list(group_idx)
+        # DISTINCT aggregates extend the integer key with the argument, so
+        # a single float key is densified for them too
         cols, group_idx, key_restore = self._densify_float_keys(
-            runtime, cols, group_idx)
+            runtime, cols, group_idx,
+            force=any(c.isDistinctAgg() for c in agg_calls))
         keyspecs = self._keyspecs_for(runtime, cols, group_idx)
 
         # bucket aggs by (filter_col_index, distinct) — aggregate.py:377-520
@@ -1477,13 +1514,13 @@ class DaskAggregatePlugin(BaseRelPlugin):
         return keyspecs
 
     @staticmethod
-    def _densify_float_keys(runtime, cols, group_idx):
+    def _densify_float_keys(runtime, cols, group_idx, force=False):
         """Composite key sets with float columns: each float key becomes a
         dense integer id (distinct floats via the bits-mode groupby, ids
         assigned by table position, joined back per row) so radix packing
         applies; the output restores the float via a host LUT. Returns
         (cols2, group_idx2, restore {key_pos: np.float64 LUT})."""
-        if len(group_idx) <= 1 or not any(
+        if (len(group_idx) <= 1 and not force) or not any(
                 cols[gi].dtype in (rt.F64, rt.F32) for gi in group_idx):
             return cols, group_idx, {}
         cols = list(cols)
@@ -1911,8 +1948,9 @@ class DaskAggregatePlugin(BaseRelPlugin):
                                                    with_validity=False)
                     finally:
                         runtime.hash_table_free(table)
+                    # scattered build positions are 4-byte ids (fid.dtype)
                     idcol = rt.DeviceColumn(runtime, fid.data,
-                                            col.validity, n_, rt.I64,
+                                            col.validity, n_, fid.dtype,
                                             owner=False,
                                             keep_alive=(fid, col))
                     cols = list(cols)
@@ -2124,7 +2162,7 @@ class DaskSortPlugin(BaseRelPlugin):
 
     def convert(self, rel, context):
         import os as _os
-        (dc,) = self.assert_inputs(rel, 1, context)
+        (dc,) = self.assert_inputs(rel, 1, context, host_ok=True)
         min_dev = int(_os.environ.get("DSX_SORT_MIN", 65536))
         if isinstance(dc, DataContainer) and dc.table.num_rows >= min_dev:
             out = self._device_sort(context, dc, rel.sort().getCollation())
@@ -2211,7 +2249,7 @@ class DaskLimitPlugin(BaseRelPlugin):
         if (below.get_current_node_type() == "Sort"
                 and node.fetch is not None
                 and (node.fetch + node.offset) * ncols_in <= nelem_limit):
-            (inp,) = self.assert_inputs(below, 1, context)
+            (inp,) = self.assert_inputs(below, 1, context, host_ok=True)
             keys = below.sort().getCollation()
             k = node.fetch + node.offset
             from dask_sql_amd.materialize import to_pandas
@@ -2225,7 +2263,7 @@ class DaskLimitPlugin(BaseRelPlugin):
             pdf = to_pandas(inp, context)
             pdf = _topk(pdf, keys, k).iloc[node.offset:]
             return HostDataContainer(pdf.reset_index(drop=True))
-        (inp,) = self.assert_inputs(rel, 1, context)
+        (inp,) = self.assert_inputs(rel, 1, context, host_ok=True)
         if isinstance(inp, HostDataContainer):
             pdf = inp.pdf
         else:
@@ -2810,10 +2848,12 @@ class DaskWindowPlugin(BaseRelPlugin):
                     .transform("size")
             elif f == "count":
                 res = grp["v"].transform("count")
+            elif f == "sum":
+                # SUM over a partition with no non-NULL value is NULL
+                res = grp["v"].transform("sum", min_count=1)
             else:
                 res = grp["v"].transform(
-                    {"sum": "sum", "avg": "mean", "min": "min",
-                     "max": "max"}[f])
+                    {"avg": "mean", "min": "min", "max": "max"}[f])
         else:
             # running aggregates, default RANGE UNBOUNDED..CURRENT frame:
             # cumulative then broadcast the tie-group's last value (peers)
@@ -2913,11 +2953,21 @@ class DaskUnionPlugin(BaseRelPlugin):
                     m.append(index.get(s, 0))
                 map_col = runtime.upload_column(np.array(m, dtype=np.int32),
                                                 dtype=rt.I32)
-                g = runtime.gather(map_col, c.data, c.len)
+                g = runtime.gather(map_col, _codes_i32(runtime, c).data,
+                                   c.len)
                 parts.append(rt.DeviceColumn(runtime, g.data, c.validity,
                                              c.len, rt.I32, owner=False,
                                              keep_alive=(g, c, map_col)))
-            out = runtime.concat_columns(parts, rt.I32)
+            code_dt = rt.I32
+            if any(p.dtype != rt.I32 for p in parts):
+                # a branch that went through a groupby (UNION's Distinct)
+                # carries wider codes: widen every part the same way
+                code_dt = rt.I64
+                prog = runtime.make_prog([(OP_COL, 0, 0)])
+                parts = [p if p.dtype == rt.I64 else runtime.eval(
+                    prog, [p], p.len, rt.I64,
+                    with_validity=bool(p.validity)) for p in parts]
+            out = runtime.concat_columns(parts, code_dt)
             out.dictionary = base
             return out
         target = cols[0].dtype

@@ -458,7 +458,10 @@ class Builder:
             return Call(op, ops, SqlType(ty))
         if kind == "scalar_sub":
             from dask_sql_amd.planner.plan import ScalarSub
-            sub = self.build_stmt(ast[1])
+            # pruned like the main plan (which never descends into it), so
+            # a CTE used both here and in FROM plans identically
+            from dask_sql_amd.planner.prune import prune_plan
+            sub = prune_plan(self.build_stmt(ast[1]))
             if len(sub.getRowType().getFieldList()) != 1:
                 raise ValueError("scalar subquery must select one column")
             return ScalarSub(sub)
@@ -1024,8 +1027,12 @@ class Builder:
                 hit = False
                 for f in plan.getRowType().getFieldList()[:n_user_fields]:
                     if (f.qualifier or "").lower() == q:
-                        items.append((("col", f.qualifier, f.getName()),
-                                      None))
+                        # a join qualifies names both sides share ("t.x");
+                        # t.* names its columns by their base name again
+                        name = f.getName()
+                        if name.lower().startswith(q + "."):
+                            name = name[len(q) + 1:]
+                        items.append((("col", f.qualifier, name), None))
                         hit = True
                 if not hit:
                     raise KeyError(f"{e[1]}.*: no columns for that "
@@ -1525,10 +1532,13 @@ class Builder:
                 base_names.append(f"{e[1].upper()}()")
             else:
                 base_names.append(None)
+        # names that differ only in case (quoted identifiers) are distinct
+        # output columns, not duplicates
         counts = {}
         for n in base_names:
             if n is not None:
-                counts[n.lower()] = counts.get(n.lower(), 0) + 1
+                counts[n] = counts.get(n, 0) + 1
+        counts = {n.lower(): c for n, c in counts.items() if c > 1}
         out_names = []
         for (e, alias), bn in zip(items, base_names):
             if alias:
@@ -1544,7 +1554,7 @@ class Builder:
         # source field qualifier
         seen = {}
         for i, n in enumerate(out_names):
-            seen.setdefault(n.lower(), []).append(i)
+            seen.setdefault(n, []).append(i)
         for n, idxs in seen.items():
             if len(idxs) > 1:
                 for i in idxs:

@@ -183,6 +183,23 @@ class AggCall(Expression):
 # ---------------------------------------------------------------------------
 # Plan nodes
 # ---------------------------------------------------------------------------
+def _signature(o, top=True):
+    if isinstance(o, LogicalPlan) and not top:
+        return o.signature()
+    if isinstance(o, (list, tuple)):
+        return tuple(_signature(x, False) for x in o)
+    if isinstance(o, dict):
+        return tuple(sorted((repr(k), _signature(v, False))
+                            for k, v in o.items()))
+    if isinstance(o, float) and o != o:
+        return "nan"
+    if hasattr(o, "__dict__") and not callable(o):
+        return (type(o).__name__,) + tuple(
+            (k, _signature(v, False)) for k, v in sorted(vars(o).items())
+            if k != "_signature")
+    return repr(o)
+
+
 class LogicalPlan:
     def __init__(self, node_type: str, inputs: list["LogicalPlan"],
                  row_type: RelDataType, payload):
@@ -229,6 +246,15 @@ class LogicalPlan:
 
     def limit(self):
         return self._get("Limit")
+
+    def signature(self):
+        """Hashable structural identity of this subtree (node types,
+        payloads, expressions, row types). Plans are immutable, so it is
+        computed once; two equal signatures compute the same relation."""
+        sig = self.__dict__.get("_signature")
+        if sig is None:
+            sig = self.__dict__["_signature"] = _signature(self)
+        return sig
 
     def explain(self, indent=0) -> str:
         s = "  " * indent + f"{self._node_type}: " \

@@ -113,9 +113,14 @@ def _prune(plan: LogicalPlan, needed):
         out_old = [i for i in needed if (i < n_l or not out_is_lhs_only)]
         new_fields = [fields[i] for i in out_old]
         output_indices = [m[i] for i in out_old]  # child-combined positions
+        new_node = JoinNode(node.getJoinType(), new_cond,
+                            output_indices=output_indices)
+        # NULL semantics ride on the node (NOT IN / INTERSECT / EXCEPT)
+        for attr in ("null_aware", "null_equal"):
+            if hasattr(node, attr):
+                setattr(new_node, attr, getattr(node, attr))
         new = LogicalPlan("Join", [new_l, new_r], RelDataType(new_fields),
-                          JoinNode(node.getJoinType(), new_cond,
-                                   output_indices=output_indices))
+                          new_node)
         out_m = {old: pos for pos, old in enumerate(out_old)}
         return new, out_m
 

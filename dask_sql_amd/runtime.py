@@ -275,7 +275,8 @@ class Runtime:
     # stack effect per opcode family (VM slots are 6 named registers —
     # dsxhip.hip VmStack; exceeding them would silently alias slot 5)
     _PUSH_OPS = {1, 2, 3, 4}          # COL, LIT_*
-    _BIN_OPS = set(range(10, 42))     # arith/cmp/AND/OR
+    # arith/cmp/AND/OR + POW(71), FLOORMOD(75), ATAN2(82): each pops two
+    _BIN_OPS = set(range(10, 42)) | {71, 75, 82}
     _SELECT_OP = 60
     _MAX_DEPTH = 8
 

@@ -6,8 +6,9 @@ changes made while the GPU pool is closed.
 Usage: python scripts/plan_audit_gpu_tests.py"""
 import inspect
 import sys
+from pathlib import Path
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 
 class _PlanOK(Exception):

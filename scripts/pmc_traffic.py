@@ -44,7 +44,8 @@ def one_pass(counter):
     subprocess.run(
         ["rocprofv3", "--pmc", counter, "-d", d, "--output-format", "csv",
          "--", "python", str(REPO / "bench.py"), "--workload", WORKLOAD,
-         "--steps", str(STEPS), "--warmup", "2", "--no-cpu-baseline"],
+         "--steps", str(STEPS), "--warmup", "2", "--full",
+         "--no-cpu-baseline"],
         cwd="/tmp", check=True, stdout=subprocess.DEVNULL,
         stderr=subprocess.DEVNULL, timeout=280)
     acc, cnt = defaultdict(float), defaultdict(int)

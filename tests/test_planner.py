@@ -822,10 +822,12 @@ def test_plan_audit_gpu_suites_cpu():
     import re
     import subprocess
     import sys
+    from pathlib import Path
 
+    repo = Path(__file__).resolve().parent.parent
     r = subprocess.run([sys.executable, "scripts/plan_audit_gpu_tests.py"],
                        capture_output=True, text=True, timeout=600,
-                       cwd="/root/repo")
+                       cwd=str(repo))
     m = re.search(r"TOTAL planned-ok (\d+), not-auditable (\d+), "
                   r"FAILED (\d+)", r.stdout)
     assert m, r.stdout[-2000:]

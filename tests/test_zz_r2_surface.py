@@ -92,7 +92,8 @@ def test_ilike_similar_escape(ctx):
                   ).compute()
     assert sorted(out["v"].astype(np.int64).tolist()) == [3]
     out = ctx.sql("SELECT v FROM tlk WHERE s NOT ILIKE '%p%'").compute()
-    assert sorted(out["v"].astype(np.int64).tolist()) == [2]
+    # neither "Banana" nor "50% off" contains a p/P
+    assert sorted(out["v"].astype(np.int64).tolist()) == [2, 3]
 
 
 def test_datetime_trunc_exec(ctx):
@@ -368,8 +369,13 @@ def test_float_key_join(ctx):
                   "ON l.x = r.x").compute()
     got = sorted(zip(out["lv"].astype(np.int64),
                      out["rv"].astype(np.int64)))
-    # pandas merge semantics: 2.5↔2.5, NaN↔NaN, -0.0↔0.0
-    assert got == [(1, 0), (2, 1), (3, 2)], got
+    # 2.5↔2.5 and -0.0↔0.0 match. A NaN in a float64 frame IS the NULL
+    # (pandas has no other), and an INNER join drops NULL keys on both
+    # sides: the reference filters `isna()` keys before its merge
+    # (rel/logical/join.py:198-213), as SQL requires and as the sqlite
+    # corpus (test_zz_sqlite_compat.py joins on NULL-bearing float keys)
+    # checks — so the NaN rows pair with nothing.
+    assert got == [(1, 0), (3, 2)], got
 
 
 def test_ref_complex_query(ctx):
