@@ -420,6 +420,13 @@ struct VmStack {
 
 // returns value in out, validity flag as return
 // returns value in out, validity flag as return
+//
+// LITE drops the ops that compile to long routines (64-bit integer and f64
+// division, sqrt, exp/log/pow, trigonometry, civil dates): with them inlined
+// a kernel needs 128 VGPRs plus scratch and runs at half occupancy. A kernel
+// instantiates both and the host picks by vm_prog_is_lite(); a LITE
+// evaluator handed such an op yields NULL like any unknown op.
+template <bool LITE = false>
 __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const ColsArg& C,
                         int64_t r, Slot& out) {
   VmStack k;
@@ -457,8 +464,20 @@ __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const Col
   k.get(sp - 2, a, av);                                                        \
   k.get(sp - 1, b, bv);                                                        \
   sp--;
+#define VM_HEAVY()                                                             \
+  if (LITE) {                                                                  \
+    out.i = 0;                                                                 \
+    return false;                                                              \
+  }
 #define BIN_F(OP, EXPR)                                                        \
   case OP: {                                                                   \
+    POP2();                                                                    \
+    res.EXPR;                                                                  \
+    k.set(sp - 1, res, av && bv);                                              \
+  } break;
+#define BIN_H(OP, EXPR)                                                        \
+  case OP: {                                                                   \
+    VM_HEAVY();                                                                \
     POP2();                                                                    \
     res.EXPR;                                                                  \
     k.set(sp - 1, res, av && bv);                                              \
@@ -466,7 +485,7 @@ __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const Col
       BIN_F(DSX_OP_ADD_F64, f = a.f + b.f)
       BIN_F(DSX_OP_SUB_F64, f = a.f - b.f)
       BIN_F(DSX_OP_MUL_F64, f = a.f * b.f)
-      BIN_F(DSX_OP_DIV_F64, f = a.f / b.f)
+      BIN_H(DSX_OP_DIV_F64, f = a.f / b.f)
       BIN_F(DSX_OP_LT_F64, i = (a.f < b.f) ? 1 : 0)
       BIN_F(DSX_OP_LE_F64, i = (a.f <= b.f) ? 1 : 0)
       BIN_F(DSX_OP_GT_F64, i = (a.f > b.f) ? 1 : 0)
@@ -476,9 +495,9 @@ __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const Col
       BIN_F(DSX_OP_ADD_I64, i = a.i + b.i)
       BIN_F(DSX_OP_SUB_I64, i = a.i - b.i)
       BIN_F(DSX_OP_MUL_I64, i = a.i * b.i)
-      BIN_F(DSX_OP_DIV_I64, i = b.i ? a.i / b.i : 0)
-      BIN_F(DSX_OP_MOD_I64, i = b.i ? a.i % b.i : 0)
-      BIN_F(DSX_OP_FLOORMOD_I64, i = b.i ? ((a.i % b.i) + b.i) % b.i : 0)
+      BIN_H(DSX_OP_DIV_I64, i = b.i ? a.i / b.i : 0)
+      BIN_H(DSX_OP_MOD_I64, i = b.i ? a.i % b.i : 0)
+      BIN_H(DSX_OP_FLOORMOD_I64, i = b.i ? ((a.i % b.i) + b.i) % b.i : 0)
       BIN_F(DSX_OP_LT_I64, i = (a.i < b.i) ? 1 : 0)
       BIN_F(DSX_OP_LE_I64, i = (a.i <= b.i) ? 1 : 0)
       BIN_F(DSX_OP_GT_I64, i = (a.i > b.i) ? 1 : 0)
@@ -486,6 +505,7 @@ __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const Col
       BIN_F(DSX_OP_EQ_I64, i = (a.i == b.i) ? 1 : 0)
       BIN_F(DSX_OP_NE_I64, i = (a.i != b.i) ? 1 : 0)
 #undef BIN_F
+#undef BIN_H
       case DSX_OP_AND: {
         // SQL 3-valued: F if either F; NULL if any NULL else T
         POP2();
@@ -562,16 +582,19 @@ __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const Col
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_EXP_F64:
+        VM_HEAVY();
         UN();
         res.f = exp(a.f);
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_LN_F64:
+        VM_HEAVY();
         UN();
         res.f = log(a.f);
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_POW_F64:
+        VM_HEAVY();
         k.get(--sp, b, bv);
         k.get(sp - 1, a, av);
         res.f = pow(a.f, b.f);
@@ -580,6 +603,7 @@ __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const Col
       case DSX_OP_YEAR:
       case DSX_OP_MONTH:
       case DSX_OP_DAY: {
+        VM_HEAVY();
         UN();
         int y, m, d;
         civil_from_days(a.i, y, m, d);
@@ -593,6 +617,7 @@ __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const Col
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_SQRT_F64:
+        VM_HEAVY();
         UN();
         res.f = sqrt(a.f);
         k.set(sp - 1, res, av);
@@ -603,42 +628,50 @@ __device__ __forceinline__ bool vm_eval(const DsxInstr* prog, int len, const Col
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_SIN_F64:
+        VM_HEAVY();
         UN();
         res.f = sin(a.f);
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_COS_F64:
+        VM_HEAVY();
         UN();
         res.f = cos(a.f);
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_TAN_F64:
+        VM_HEAVY();
         UN();
         res.f = tan(a.f);
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_ASIN_F64:
+        VM_HEAVY();
         UN();
         res.f = asin(a.f);
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_ACOS_F64:
+        VM_HEAVY();
         UN();
         res.f = acos(a.f);
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_ATAN_F64:
+        VM_HEAVY();
         UN();
         res.f = atan(a.f);
         k.set(sp - 1, res, av);
         break;
       case DSX_OP_ATAN2_F64:
+        VM_HEAVY();
         k.get(--sp, b, bv);
         k.get(sp - 1, a, av);
         res.f = atan2(a.f, b.f);
         k.set(sp - 1, res, av && bv);
         break;
 #undef UN
+#undef VM_HEAVY
       case DSX_OP_SELECT: {
         // (cond, a, b): cond true→a, false/NULL→b (CASE WHEN semantics)
         k.get(sp - 3, c, cv);
@@ -689,6 +722,24 @@ struct ProgArg {
   int32_t len;
 };
 
+// no op that vm_eval<true> leaves out (see vm_eval)
+static bool vm_prog_is_lite(const DsxInstr* prog, int len) {
+  for (int i = 0; i < len; i++) {
+    switch (prog[i].op) {
+      case DSX_OP_DIV_F64: case DSX_OP_DIV_I64: case DSX_OP_MOD_I64:
+      case DSX_OP_FLOORMOD_I64: case DSX_OP_SQRT_F64: case DSX_OP_EXP_F64:
+      case DSX_OP_LN_F64: case DSX_OP_POW_F64: case DSX_OP_YEAR:
+      case DSX_OP_MONTH: case DSX_OP_DAY: case DSX_OP_SIN_F64:
+      case DSX_OP_COS_F64: case DSX_OP_TAN_F64: case DSX_OP_ASIN_F64:
+      case DSX_OP_ACOS_F64: case DSX_OP_ATAN_F64: case DSX_OP_ATAN2_F64:
+        return false;
+      default:
+        break;
+    }
+  }
+  return true;
+}
+
 // ---------------------------------------------------------------------------
 // dsx_eval — projection (project.py:56-65)
 // ---------------------------------------------------------------------------
@@ -737,6 +788,7 @@ extern "C" int dsx_eval(DsxCtx* c, const DsxInstr* prog, int prog_len,
 // dsx_filter — predicate + ORDER-PRESERVING compaction (filter.py:20-45)
 // two passes over a wave64 ballot bitmask
 // ---------------------------------------------------------------------------
+template <bool LITE>
 __global__ void k_filter_mask(ProgArg prog, ColsArg C, int64_t n,
                               uint64_t* mask, int64_t* block_counts) {
   int64_t lo, hi;
@@ -756,7 +808,7 @@ __global__ void k_filter_mask(ProgArg prog, ColsArg C, int64_t n,
     bool pred = false;
     if (r < n) {
       Slot v;
-      bool valid = vm_eval(prog.ins, prog.len, C, r, v);
+      bool valid = vm_eval<LITE>(prog.ins, prog.len, C, r, v);
       pred = valid && v.i != 0;  // NULL → False (filter.py:39)
     }
     uint64_t m = __ballot(pred);
@@ -957,8 +1009,10 @@ extern "C" int dsx_filter_cols(DsxCtx* c, const DsxInstr* prog, int prog_len,
       (FilterMatArg*)((char*)c->scratch + ((arg_off + 63) / 64) * 64);
   if (grid > 0) {
     ProfScope ps(c, "k_filter_mask");
-    hipLaunchKernelGGL(k_filter_mask, dim3(grid), dim3(BLOCK), 0, c->stream,
-                       P, C, n, mask, block_counts);
+    hipLaunchKernelGGL(vm_prog_is_lite(prog, prog_len) ? k_filter_mask<true>
+                                                       : k_filter_mask<false>,
+                       dim3(grid), dim3(BLOCK), 0, c->stream, P, C, n, mask,
+                       block_counts);
   }
   hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream,
                      block_counts, grid, total);
@@ -1031,8 +1085,10 @@ extern "C" int dsx_filter(DsxCtx* c, const DsxInstr* prog, int prog_len,
   int64_t* total = block_counts + grid;
   {
     ProfScope ps(c, "k_filter_mask");
-    hipLaunchKernelGGL(k_filter_mask, dim3(grid), dim3(BLOCK), 0, c->stream, P,
-                       C, n, mask, block_counts);
+    hipLaunchKernelGGL(vm_prog_is_lite(prog, prog_len) ? k_filter_mask<true>
+                                                       : k_filter_mask<false>,
+                       dim3(grid), dim3(BLOCK), 0, c->stream, P, C, n, mask,
+                       block_counts);
   }
   hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream,
                      block_counts, grid, total);
@@ -1328,11 +1384,9 @@ __global__ void k_keypack(KeyArg K, ColsArg C, int64_t n, uint64_t* out) {
   }
 }
 
-extern "C" int dsx_keypack(DsxCtx* c, const DsxColumn* cols, int ncols,
-                           const DsxKeySpec* keys, int nkeys, int64_t n,
-                           uint64_t* out_codes) {
-  if (nkeys > DSX_MAX_KEYS || ncols > DSX_MAX_COLS) FAIL(-3, "too many keys");
-  KeyArg K{};
+// per-key strides of the packed code (shared by every entry that packs keys,
+// so their codes are bit-identical)
+static int make_keyarg(const DsxKeySpec* keys, int nkeys, KeyArg& K) {
   K.nkeys = nkeys;
   uint64_t stride = 1;
   for (int j = 0; j < nkeys; j++) {
@@ -1347,6 +1401,16 @@ extern "C" int dsx_keypack(DsxCtx* c, const DsxColumn* cols, int ncols,
     if (stride > (1ull << 62) / range) FAIL(-4, "key space exceeds 2^62");
     stride *= range;
   }
+  return 0;
+}
+
+extern "C" int dsx_keypack(DsxCtx* c, const DsxColumn* cols, int ncols,
+                           const DsxKeySpec* keys, int nkeys, int64_t n,
+                           uint64_t* out_codes) {
+  if (nkeys > DSX_MAX_KEYS || ncols > DSX_MAX_COLS) FAIL(-3, "too many keys");
+  KeyArg K{};
+  int rc = make_keyarg(keys, nkeys, K);
+  if (rc) return rc;
   ColsArg C{};
   C.ncols = ncols;
   for (int i = 0; i < ncols; i++) {
@@ -1914,6 +1978,260 @@ extern "C" int dsx_hash_probe_cols(
   HIP_TRY(hipGetLastError());
   *out_count = total;
   return dbg_check(c, "dsx_hash_probe_cols");
+}
+
+// ---------------------------------------------------------------------------
+// dsx_filter_probe_cols — scan filter + key pack + PK-FK probe in one sweep
+// over the UNFILTERED probe columns (INNER, unique build keys). Replaces
+// dsx_filter_cols → dsx_keypack → dsx_hash_probe_cols and their three
+// intermediates (compacted columns, code column, slot/count cache) with a
+// one-bit-per-row match mask.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool fp_key_valid(const KeyArg& K, const ColsArg& C,
+                                             int64_t r) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < DSX_MAX_KEYS; j++) {
+    if (j >= K.nkeys) break;
+    const uint8_t* v = C.validity[K.k[j].col];
+    if (v && !v[r]) ok = false;  // NULL key never matches (join.py:202-213)
+  }
+  return ok;
+}
+
+// first match of `cde` (build keys are unique on this path)
+__device__ __forceinline__ bool fp_probe(const uint64_t* tkeys,
+                                         const uint32_t* tvals, int64_t mask,
+                                         int packed, uint64_t cde,
+                                         uint32_t& bid) {
+  int64_t s = (int64_t)(mix64(cde) & mask);
+  while (true) {
+    uint64_t k = tkeys[s];
+    if (k == EMPTY_KEY) return false;
+    if ((packed ? (k >> 32) : k) == cde) {
+      bid = packed ? (uint32_t)k : tvals[s];
+      return true;
+    }
+    s = (s + 1) & mask;
+  }
+}
+
+// pass 1: predicate → key validity → pack → probe → ballot. Same word
+// ownership as k_filter_mask (and the same round-up for idle blocks); waves
+// run free, no barrier in the row loop. extra[0] receives the table's dup
+// flag so the host fetches it with the total in one copy.
+template <bool LITE>
+__global__ void k_fprobe_mask(ProgArg prog, KeyArg K, ColsArg C, int64_t n,
+                              const uint64_t* tkeys, const uint32_t* tvals,
+                              int64_t tmask, int packed,
+                              const unsigned int* dup, uint64_t* mask,
+                              int64_t* block_counts, int64_t* extra) {
+  int64_t lo, hi;
+  block_range(n, 64, lo, hi);
+  __shared__ int64_t s_count;
+  if (threadIdx.x == 0) {
+    s_count = 0;
+    if (blockIdx.x == 0) extra[0] = (int64_t)*dup;
+  }
+  __syncthreads();
+  int lane = threadIdx.x & 63;
+  int64_t local = 0;
+  for (int64_t w = (lo + 63) / 64 + threadIdx.x / 64; w * 64 < hi;
+       w += WAVES_PER_BLOCK) {
+    int64_t r = w * 64 + lane;
+    bool hit = false;
+    if (r < n) {
+      Slot v;
+      bool valid = vm_eval<LITE>(prog.ins, prog.len, C, r, v);
+      if (valid && v.i != 0 && fp_key_valid(K, C, r)) {  // NULL → False
+        uint32_t bid;
+        hit = fp_probe(tkeys, tvals, tmask, packed, pack_key(K, C, r), bid);
+      }
+    }
+    uint64_t m = __ballot(hit);
+    if (lane == 0) {
+      mask[w] = m;
+      local += __popcll(m);
+    }
+  }
+  if (lane == 0) atomicAdd((unsigned long long*)&s_count, (unsigned long long)local);
+  __syncthreads();
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = s_count;
+}
+
+// position of the k-th (0-based) set bit of m; k < popcount(m)
+__device__ __forceinline__ int fp_select_bit(uint64_t m, int k) {
+  int pos = 0;
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    int cnt = __popcll(m & ((1ull << w) - 1));
+    if (k >= cnt) {
+      k -= cnt;
+      m >>= w;
+      pos += w;
+    }
+  }
+  return pos;
+}
+
+// pass 2: each wave takes a CONTIGUOUS quarter of the block's mask words.
+// Up front the waves count their quarters and exchange the four totals
+// through LDS (the only barrier); after that a wave scans 64 words at a time
+// with shuffles and hands the j-th matched row of the batch to lane j, so
+// lanes stay dense at any match density, output slots are consecutive across
+// the wave (coalesced stores) and rows come out in increasing probe order.
+// Only matched rows re-pack and re-probe to recover the build row id.
+__global__ void k_fprobe_emit(KeyArg K, ColsArg C, int64_t n,
+                              const uint64_t* tkeys, const uint32_t* tvals,
+                              int64_t tmask, int packed, const uint64_t* mask,
+                              const int64_t* block_offsets,
+                              const JoinMatArg* Mp, int64_t total,
+                              unsigned int* dbg) {
+  __shared__ JoinMatArg s_M;  // LDS copy (see k_hash_probe_mat note)
+  __shared__ int64_t s_tot[WAVES_PER_BLOCK];
+  int64_t lo, hi;
+  block_range(n, 64, lo, hi);
+  int lane = threadIdx.x & 63;
+  int wid = threadIdx.x >> 6;
+  int64_t w0 = (lo + 63) / 64, w1 = (hi + 63) / 64;  // lo == hi ⇒ no words
+  int64_t q = (w1 - w0 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+  int64_t c0 = min(w1, w0 + wid * q), c1 = min(w1, c0 + q);
+  int64_t mine = 0;
+  for (int64_t w = c0 + lane; w < c1; w += 64) mine += __popcll(mask[w]);
+  for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d, 64);
+  if (lane == 0) s_tot[wid] = mine;
+  if (threadIdx.x == 0) s_M = *Mp;
+  __syncthreads();
+  const JoinMatArg& M = s_M;
+  int64_t base = block_offsets[blockIdx.x];
+  for (int i = 0; i < wid; i++) base += s_tot[i];
+  for (int64_t wb = c0; wb < c1; wb += 64) {
+    uint64_t m = (wb + lane < c1) ? mask[wb + lane] : 0;
+    int cnt = __popcll(m);
+    int inc = cnt;  // inclusive prefix of the batch's word counts
+    for (int d = 1; d < 64; d <<= 1) {
+      int t = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += t;
+    }
+    int exc = inc - cnt;
+    int T = __shfl(inc, 63, 64);
+    uint32_t m_lo = (uint32_t)m, m_hi = (uint32_t)(m >> 32);
+    for (int j0 = 0; j0 < T; j0 += 64) {
+      // all lanes search (shuffles stay outside divergent code); lanes past
+      // the batch total search for its last row and then sit out
+      int j = min(j0 + lane, T - 1);
+      int L = 0;  // smallest lane whose inclusive count exceeds j
+      for (int step = 32; step > 0; step >>= 1) {
+        int v = __shfl(inc, L + step - 1, 64);
+        if (v <= j) L += step;
+      }
+      uint64_t mL = ((uint64_t)(uint32_t)__shfl((int)m_hi, L, 64) << 32) |
+                    (uint32_t)__shfl((int)m_lo, L, 64);
+      int k = j - __shfl(exc, L, 64);
+      if (j0 + lane < T) {
+        int64_t r = (wb + L) * 64 + fp_select_bit(mL, k);
+        int64_t o = base + j;
+        uint32_t bid = DSX_NULL_IDX;
+        bool hit = r < n && fp_probe(tkeys, tvals, tmask, packed,
+                                     pack_key(K, C, r), bid);
+        if (!hit || o >= total) atomicOr(dbg, 2u);
+        else jm_write(M, o, r, bid);
+      }
+    }
+    base += T;
+  }
+}
+
+extern "C" int dsx_filter_probe_cols(
+    DsxCtx* c, DsxHashTable* t, const DsxInstr* prog, int prog_len,
+    const DsxColumn* cols, int ncols, const DsxKeySpec* keys, int nkeys,
+    int64_t n, const DsxColumn* pcols, int n_pcols, const DsxColumn* bcols,
+    int n_bcols, void** out_datas, uint8_t** out_valids, int64_t* out_count) {
+  if (prog_len > DSX_MAX_PROG || ncols > DSX_MAX_COLS || nkeys > DSX_MAX_KEYS)
+    FAIL(-3, "filter-probe spec too large");
+  int nmats = n_pcols + n_bcols;
+  if (nmats > 16) FAIL(-3, "too many join output columns for fused emit");
+  *out_count = 0;
+  ProgArg P{};
+  memcpy(P.ins, prog, prog_len * sizeof(DsxInstr));
+  P.len = prog_len;
+  KeyArg K{};
+  int rc = make_keyarg(keys, nkeys, K);
+  if (rc) return rc;
+  for (int j = 0; j < nkeys; j++)
+    if (keys[j].mode != 0 || keys[j].col < 0 || keys[j].col >= ncols)
+      FAIL(-3, "filter-probe takes radix-packed integer keys only");
+  ColsArg C{};
+  C.ncols = ncols;
+  for (int i = 0; i < ncols; i++) {
+    C.data[i] = cols[i].data;
+    C.validity[i] = cols[i].validity;
+    C.dtype[i] = cols[i].dtype;
+  }
+  int64_t nwords = (n + 63) / 64;
+  int grid = (int)min((int64_t)MAX_GRID, (nwords + WAVES_PER_BLOCK - 1) /
+                                             WAVES_PER_BLOCK);
+  int64_t arg_off = nwords * 8 + (grid + 2) * 8 + 64;
+  rc = ensure_scratch(c, arg_off + (int64_t)sizeof(JoinMatArg) + 64);
+  if (rc) return rc;
+  uint64_t* mask = (uint64_t*)c->scratch;
+  int64_t* block_counts = (int64_t*)(mask + nwords);
+  int64_t* d_total = block_counts + grid;  // [0] total, [1] dup flag
+  JoinMatArg* d_M =
+      (JoinMatArg*)((char*)c->scratch + ((arg_off + 63) / 64) * 64);
+  int64_t h_res[2] = {0, 0};
+  if (grid > 0) {
+    {
+      ProfScope ps(c, "k_fprobe_mask");
+      auto kern = vm_prog_is_lite(prog, prog_len) ? k_fprobe_mask<true>
+                                                  : k_fprobe_mask<false>;
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, c->stream, P, K, C,
+                         n, t->keys, t->vals, t->slots - 1, t->packed, t->dup,
+                         mask, block_counts, d_total + 1);
+    }
+    hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream,
+                       block_counts, grid, d_total);
+    HIP_TRY(hipMemcpyAsync(h_res, d_total, 16, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // duplicate build keys: one match bit per row is not enough
+    if (h_res[1] != 0) return DSX_NOT_APPLICABLE;
+  }
+  int64_t total = h_res[0];
+  JoinMatArg M{};
+  M.ncols = nmats;
+  int64_t tsz = total > 0 ? total : 1;
+  for (int i = 0; i < nmats; i++) {
+    const DsxColumn* src = i < n_pcols ? &pcols[i] : &bcols[i - n_pcols];
+    int esz = src->dtype == DSX_I64 || src->dtype == DSX_F64 ? 8
+              : src->dtype == DSX_I32 || src->dtype == DSX_F32 ? 4 : 1;
+    int rc2 = pool_alloc(c, tsz * esz, &out_datas[i]);
+    if (rc2) return rc2;
+    out_valids[i] = nullptr;
+    if (src->validity) {
+      void* vp = nullptr;
+      rc2 = pool_alloc(c, tsz, &vp);
+      if (rc2) return rc2;
+      out_valids[i] = (uint8_t*)vp;
+    }
+    M.src[i] = src->data;
+    M.srcv[i] = src->validity;
+    M.dst[i] = out_datas[i];
+    M.dstv[i] = out_valids[i];
+    M.dtype[i] = src->dtype;
+    M.side[i] = i < n_pcols ? 0 : 1;
+  }
+  if (grid > 0 && total > 0) {
+    HIP_TRY(hipMemcpyAsync(d_M, &M, sizeof(JoinMatArg), hipMemcpyHostToDevice,
+                           c->stream));
+    ProfScope ps(c, "k_fprobe_emit");
+    hipLaunchKernelGGL(k_fprobe_emit, dim3(grid), dim3(BLOCK), 0, c->stream,
+                       K, C, n, t->keys, t->vals, t->slots - 1, t->packed,
+                       mask, block_counts, d_M, total, c->dbg_flag);
+  }
+  HIP_TRY(hipGetLastError());
+  *out_count = total;
+  return dbg_check(c, "dsx_filter_probe_cols");
 }
 
 template <int PASS>

@@ -90,6 +90,12 @@ class DataContainer:
     def df(self):
         return self.table
 
+    def with_columns(self, column_container) -> "DataContainer":
+        """Same rows under another column container (rename / subset)."""
+        dc = DataContainer(self.table, column_container)
+        dc.base_scan = getattr(self, "base_scan", False)
+        return dc
+
     def backend_cols(self):
         """Device columns in FRONTEND order (what InputRef indices mean)."""
         cc = self.column_container
@@ -104,6 +110,51 @@ class DataContainer:
             c: self.table.col(cc.get_backend_by_frontend_name(c))
             for c in cc.columns
         })
+
+
+class DeferredFilter(DataContainer):
+    """A WHERE over a base table that has not run yet: the base container
+    plus the compiled predicate. A join that probes with it fuses the
+    predicate into the probe sweep (dsx_filter_probe_cols) and never builds
+    the filtered table; every other consumer reads `.table`, which runs the
+    ordinary fused filter (dsx_filter_cols) once and caches the result, so
+    it sees exactly what an eager filter would have produced.
+
+    prog is the predicate as (op, arg0, imm) tuples over prog_cols (device
+    columns of the base table). Views created by with_columns share the
+    materialized table through `_state`."""
+
+    def __init__(self, base: DataContainer, column_container, prog,
+                 prog_cols, materialize, _state=None):
+        self.base = base
+        self.column_container = column_container
+        self.prog = tuple(prog)
+        self.prog_cols = list(prog_cols)
+        self._materialize = materialize
+        self._state = _state if _state is not None else {"table": None}
+
+    @property
+    def materialized(self) -> bool:
+        return self._state["table"] is not None
+
+    @property
+    def table(self) -> DeviceTable:
+        if self._state["table"] is None:
+            self._state["table"] = self._materialize(self)
+        return self._state["table"]
+
+    @property
+    def max_rows(self) -> int:
+        """Upper bound of the row count, known without running the filter."""
+        return self.base.table.num_rows
+
+    def with_columns(self, column_container) -> "DeferredFilter":
+        return DeferredFilter(self.base, column_container, self.prog,
+                              self.prog_cols, self._materialize, self._state)
+
+    def unfiltered(self) -> DataContainer:
+        """The base rows under this container's column names."""
+        return DataContainer(self.base.table, self.column_container)
 
 
 class HostDataContainer:

@@ -12,7 +12,8 @@ import numpy as np
 
 from dask_sql_amd import runtime as rt
 from dask_sql_amd.datacontainer import (ColumnContainer, DataContainer,
-                                        DeviceTable, HostDataContainer)
+                                        DeferredFilter, DeviceTable,
+                                        HostDataContainer)
 from dask_sql_amd.physical.convert import BaseRelPlugin, RelConverter
 from dask_sql_amd.physical.rex import (KB, KF, KI, OP_AND, OP_COL,
                                        OP_IS_NOT_NULL, OP_NOT,
@@ -215,6 +216,94 @@ def _eval_udf_nodes(expr, cols, runtime, context):
     return InputRef(len(cols) - 1, SqlType(ret_sql))
 
 
+def _unique_backends(cc):
+    backends = []
+    for f in cc.columns:
+        b = cc.get_backend_by_frontend_name(f)
+        if b not in backends:
+            backends.append(b)
+    return backends
+
+
+def _pending_filter(dc) -> bool:
+    return isinstance(dc, DeferredFilter) and not dc.materialized
+
+
+def _run_deferred_filter(d: DeferredFilter) -> DeviceTable:
+    """First `.table` access of a DeferredFilter: the ordinary fused filter
+    (dsx_filter_cols) over the base container's columns."""
+    base = d.base
+    runtime = d.prog_cols[0].rt
+    backends = _unique_backends(base.column_container)
+    mats = [base.table.col(b) for b in backends]
+    out_list, count = runtime.filter_cols(
+        runtime.make_prog(d.prog), d.prog_cols, base.table.num_rows, mats)
+    out_cols = {}
+    for b, src, col in zip(backends, mats, out_list):
+        if getattr(src, "dictionary", None) is not None:
+            col.dictionary = src.dictionary
+        col._stats_src = src
+        out_cols[b] = col
+    return DeviceTable(out_cols, num_rows=count)
+
+
+def _has_udf(expr) -> bool:
+    if not hasattr(expr, "getOperands") or not hasattr(expr,
+                                                       "getOperatorName"):
+        return False
+    name = expr.getOperatorName()
+    if isinstance(name, str) and name.startswith("UDF:"):
+        return True
+    return any(_has_udf(o) for o in expr.getOperands())
+
+
+def _defer_filter(runtime, dc, condition, context):
+    """WHERE over a base-table scan → DeferredFilter (None = filter now).
+    A second WHERE over a pending one joins it as a conjunction: a filter
+    keeps a row only when its predicate is TRUE, so (p1 AND p2) keeps
+    exactly the rows that p2 keeps of what p1 kept."""
+    import os as _os
+    if _os.environ.get("DSX_DISABLE_FILTERPROBE"):
+        return None
+    if _has_udf(condition):
+        return None  # UDF nodes evaluate through the host, eagerly
+    pending = _pending_filter(dc)
+    if not pending and not getattr(dc, "base_scan", False):
+        return None
+    src = dc.unfiltered() if pending else dc
+    base = dc.base if pending else dc
+    if len(_unique_backends(base.column_container)) > 16:
+        return None
+    cols = src.backend_cols()
+    if not cols:
+        return None
+    prog, _ = compile_expr(condition, cols, _dicts_of(cols))
+    prog = [tuple(ins) for ins in prog]
+    # keep only the columns the predicate reads (the join adds its key
+    # columns to this list, and the kernels take 16 at most)
+    merged = list(dc.prog_cols) if pending else []
+    remap = {}
+    for a in sorted({a for op, a, _ in prog if op == OP_COL}):
+        j = next((k for k, m in enumerate(merged) if m is cols[a]), None)
+        if j is None:
+            merged.append(cols[a])
+            j = len(merged) - 1
+        remap[a] = j
+    prog = [(op, remap[a], imm) if op == OP_COL else (op, a, imm)
+            for op, a, imm in prog]
+    if pending:
+        prog = list(dc.prog) + prog + [(OP_AND, 0, 0)]
+    cols = merged
+    if not cols or len(cols) > rt.MAX_COLS:
+        return None
+    try:
+        runtime.make_prog(prog)  # length / stack-depth limits
+    except rt.DsxError:
+        return None
+    return DeferredFilter(base, dc.column_container, prog, cols,
+                          _run_deferred_filter)
+
+
 def _apply_filter(runtime, dc: DataContainer, condition,
                   context=None) -> DataContainer:
     """filter_or_scalar semantics (reference filter.py:20-45). Fused path:
@@ -224,16 +313,15 @@ def _apply_filter(runtime, dc: DataContainer, condition,
     s = scalar_literal(condition)
     if s is not None:
         return dc if s else _empty_like(runtime, dc)
+    deferred = _defer_filter(runtime, dc, condition, context)
+    if deferred is not None:
+        return deferred
     cols = dc.backend_cols()
     if context is not None and context.catalog.functions:
         condition = _eval_udf_nodes(condition, cols, runtime, context)
     prog, kind = compile_expr(condition, cols, _dicts_of(cols))
     cc = dc.column_container
-    backends = []
-    for f in cc.columns:
-        b = cc.get_backend_by_frontend_name(f)
-        if b not in backends:
-            backends.append(b)
+    backends = _unique_backends(cc)
     mats = [dc.table.col(b) for b in backends]
     if len(mats) <= 16:
         out_list, count = runtime.filter_cols(runtime.make_prog(prog), cols,
@@ -265,10 +353,11 @@ class DaskTableScanPlugin(BaseRelPlugin):
         if scan.containsProjections():
             cc = cc.limit_to(scan.getTableScanProjects())
         dc = DataContainer(table, cc)
+        dc.base_scan = True  # a WHERE over it may be deferred into a join
         for f in scan.getFilters():
             dc = _apply_filter(context._get_runtime(), dc, f)
         cc = self.fix_column_to_row_type(dc.column_container, rel.getRowType())
-        return DataContainer(dc.table, cc)
+        return dc.with_columns(cc)
 
 
 class DaskFilterPlugin(BaseRelPlugin):
@@ -282,7 +371,7 @@ class DaskFilterPlugin(BaseRelPlugin):
         condition = _resolve_scalar_subs(rel.filter().getCondition(), context)
         dc = _apply_filter(context._get_runtime(), dc, condition, context)
         cc = self.fix_column_to_row_type(dc.column_container, rel.getRowType())
-        return DataContainer(dc.table, cc)
+        return dc.with_columns(cc)
 
 
 class DaskProjectPlugin(BaseRelPlugin):
@@ -406,8 +495,8 @@ class DaskJoinPlugin(BaseRelPlugin):
         dc_lhs, dc_rhs = self.assert_inputs(rel, 2, context)
         cc_lhs = dc_lhs.column_container.make_unique("lhs")
         cc_rhs = dc_rhs.column_container.make_unique("rhs")
-        dc_lhs = DataContainer(dc_lhs.table, cc_lhs)
-        dc_rhs = DataContainer(dc_rhs.table, cc_rhs)
+        dc_lhs = dc_lhs.with_columns(cc_lhs)
+        dc_rhs = dc_rhs.with_columns(cc_rhs)
         n_lhs_cols = len(cc_lhs.columns)
 
         join_type = self.JOIN_TYPE_MAPPING[str(join.getJoinType())]
@@ -457,7 +546,19 @@ class DaskJoinPlugin(BaseRelPlugin):
         # outgrows the XCD L2, partition both sides and probe LDS-resident
         # bucket tables instead (dsx_radix_join)
         null_eq = bool(getattr(join, "null_equal", False))
-        if (lhs_on and not residual and not null_eq and len(mat_idx) <= 16
+        # FILTER-PROBE: a probe side that is a still-pending WHERE over a
+        # base table runs its predicate inside the probe sweep
+        # (dsx_filter_probe_cols); DSX_DISABLE_FILTERPROBE=1 restores the
+        # separate filter → keypack → probe passes
+        fprobe = None
+        if (join_type == "inner" and lhs_on and not residual and not null_eq
+                and len(mat_idx) <= 16
+                and not _os.environ.get("DSX_DISABLE_JOINFUSE")
+                and not _os.environ.get("DSX_DISABLE_FILTERPROBE")):
+            fprobe = self._filter_probe_side(dc_lhs, dc_rhs)
+        if (fprobe is None
+                and lhs_on and not residual and not null_eq
+                and len(mat_idx) <= 16
                 and not _os.environ.get("DSX_DISABLE_RADIX")
                 and join_type in ("inner", "left", "right", "leftanti")):
             gathered, n_out = self._radix_join(
@@ -470,7 +571,7 @@ class DaskJoinPlugin(BaseRelPlugin):
                 and join_type in ("inner", "left", "right", "leftanti")):
             gathered, n_out = self._equi_join_fused(
                 runtime, dc_lhs, dc_rhs, lhs_on, rhs_on, join_type,
-                combined, mat_idx, cc_lhs, cc_rhs)
+                combined, mat_idx, cc_lhs, cc_rhs, fprobe=fprobe)
 
         if gathered is None:
             if lhs_on:
@@ -989,12 +1090,47 @@ class DaskJoinPlugin(BaseRelPlugin):
             gathered[i] = col
         return gathered, n_out
 
+    @staticmethod
+    def _filter_probe_side(dc_lhs, dc_rhs):
+        """Which side ("l"/"r") an INNER join probes with a pending WHERE
+        fused in, or None. The probe side is the larger one; a pending
+        filter's row count is not known before it runs, so it stands in with
+        its base table's. A pending side that comes out as the build side
+        simply materializes. The radix path keeps priority: where both
+        sides could pass its build-size gate the filters run first, as
+        before, and the gate sees the real counts."""
+        import os as _os
+        pend_l, pend_r = _pending_filter(dc_lhs), _pending_filter(dc_rhs)
+        if not (pend_l or pend_r):
+            return None
+        n_l = dc_lhs.max_rows if pend_l else dc_lhs.table.num_rows
+        n_r = dc_rhs.max_rows if pend_r else dc_rhs.table.num_rows
+        if (not _os.environ.get("DSX_DISABLE_RADIX") and min(n_l, n_r) >= int(
+                _os.environ.get("DSX_RADIX_MIN_BUILD", 8_000_000))):
+            return None
+        if n_l < n_r:  # same rule as the swap below: probe with the larger
+            return "r" if pend_r else None
+        return "l" if pend_l else None
+
     def _equi_join_fused(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                         join_type, combined, mat_idx, cc_lhs, cc_rhs):
+                         join_type, combined, mat_idx, cc_lhs, cc_rhs,
+                         fprobe=None):
         """Equi join with fused emit+materialization (dsx_hash_probe_cols):
         the probe's emit pass writes the output columns directly. Returns
         ({combined_idx: DeviceColumn}, n_out) or (None, 0) on unsupported
-        shapes (caller falls back to the pair path)."""
+        shapes (caller falls back to the pair path).
+
+        fprobe "l"/"r": that side is a pending DeferredFilter and the probe
+        side of an INNER join — keys, ranges and sources then come from its
+        UNFILTERED base columns and the predicate runs inside the probe
+        (dsx_filter_probe_cols). The ranges are the base columns' cached
+        stats either way (_stats_src), so codes and table layout do not
+        change."""
+        pending = {"l": dc_lhs, "r": dc_rhs}.get(fprobe)
+        if fprobe == "l":
+            dc_lhs = dc_lhs.unfiltered()
+        elif fprobe == "r":
+            dc_rhs = dc_rhs.unfiltered()
         lcols = dc_lhs.backend_cols()
         rcols = dc_rhs.backend_cols()
         for i in lhs_on:
@@ -1019,9 +1155,12 @@ class DaskJoinPlugin(BaseRelPlugin):
                 mn, mx = min(lmn, rmn), max(lmx, rmx)
             ranges.append((mn, mx - mn + 1))
 
-        swap = join_type == "right" or (
-            join_type == "inner"
-            and dc_lhs.table.num_rows < kdc_rhs.table.num_rows)
+        if fprobe is not None:
+            swap = fprobe == "r"
+        else:
+            swap = join_type == "right" or (
+                join_type == "inner"
+                and dc_lhs.table.num_rows < kdc_rhs.table.num_rows)
         if swap:
             probe_kdc, build_kdc = kdc_rhs, dc_lhs
             probe_on, build_on = rhs_on, lhs_on
@@ -1034,10 +1173,29 @@ class DaskJoinPlugin(BaseRelPlugin):
                 "leftanti": rt.JOIN_LEFTANTI,
             }[join_type]
 
+        # probe-side program columns + key columns in ONE list for the
+        # fused entry (16 at most, else filter first)
+        fp_cols = fp_keys = None
+        if pending is not None:
+            fp_cols = list(pending.prog_cols)
+            fp_keys = []
+            pk = probe_kdc.backend_cols()
+            for pi, (mn, rng) in zip(probe_on, ranges):
+                ci = next((k for k, c in enumerate(fp_cols) if c is pk[pi]),
+                          None)
+                if ci is None:
+                    fp_cols.append(pk[pi])
+                    ci = len(fp_cols) - 1
+                fp_keys.append((ci, mn, rng, False))
+            if len(fp_cols) > rt.MAX_COLS:
+                return self._equi_join_fused(
+                    runtime, *self._materialized(fprobe, pending, dc_lhs,
+                                                 dc_rhs),
+                    lhs_on, rhs_on, join_type, combined, mat_idx, cc_lhs,
+                    cc_rhs)
+
         bcodes, bval, bkeep, space = self._key_codes(
             runtime, build_kdc, build_on, ranges)
-        pcodes, pval, pkeep, _ = self._key_codes(
-            runtime, probe_kdc, probe_on, ranges)
         # assemble per-side materialization lists (sources: ORIGINAL tables)
         probe_is_l = not swap
         p_items, b_items = [], []
@@ -1053,10 +1211,37 @@ class DaskJoinPlugin(BaseRelPlugin):
             (p_items if on_probe else b_items).append((i, col))
         table = runtime.hash_build(bcodes, bval, code_max=space - 1)
         try:
-            cols_out, n_out = runtime.hash_probe_cols(
-                table, pcodes, ktype, pval,
-                [c for _, c in p_items], [c for _, c in b_items],
-                force_build_validity=(ktype == rt.JOIN_LEFT))
+            res = None
+            if pending is not None:
+                res = runtime.filter_probe_cols(
+                    table, runtime.make_prog(pending.prog), fp_cols, fp_keys,
+                    pending.max_rows, [c for _, c in p_items],
+                    [c for _, c in b_items])
+                if res is None:
+                    # duplicate build keys: run the filter after all and
+                    # probe the same table the two-pass way
+                    dc_l2, dc_r2 = self._materialized(fprobe, pending,
+                                                      dc_lhs, dc_rhs)
+                    if swap:
+                        probe_kdc, _ = self._reconcile_dict_keys(
+                            runtime, dc_l2, dc_r2, lhs_on, rhs_on)
+                    else:
+                        probe_kdc = dc_l2
+                    src_dc, src_cc = (dc_r2, cc_rhs) if swap \
+                        else (dc_l2, cc_lhs)
+                    p_items = [
+                        (i, src_dc.table.col(
+                            src_cc.get_backend_by_frontend_name(
+                                combined[i][1])))
+                        for i, _ in p_items]
+            if res is None:
+                pcodes, pval, pkeep, _ = self._key_codes(
+                    runtime, probe_kdc, probe_on, ranges)
+                res = runtime.hash_probe_cols(
+                    table, pcodes, ktype, pval,
+                    [c for _, c in p_items], [c for _, c in b_items],
+                    force_build_validity=(ktype == rt.JOIN_LEFT))
+            cols_out, n_out = res
         finally:
             runtime.hash_table_free(table)
         gathered = {}
@@ -1066,6 +1251,12 @@ class DaskJoinPlugin(BaseRelPlugin):
             col._stats_src = src
             gathered[i] = col
         return gathered, n_out
+
+    @staticmethod
+    def _materialized(fprobe, pending, dc_lhs, dc_rhs):
+        """(dc_lhs, dc_rhs) with the pending side's filter run."""
+        done = DataContainer(pending.table, pending.column_container)
+        return (done, dc_rhs) if fprobe == "l" else (dc_lhs, done)
 
     def _cross_join(self, runtime, dc_lhs, dc_rhs, join_type):
         # reference join.py:133-140 (merge on constant); tiny-only guard

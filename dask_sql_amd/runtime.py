@@ -43,6 +43,7 @@ AGG_MIN_F64, AGG_MAX_F64, AGG_MIN_I64, AGG_MAX_I64 = 3, 4, 5, 6
 
 JOIN_INNER, JOIN_LEFT, JOIN_LEFTSEMI, JOIN_LEFTANTI = 0, 1, 2, 3
 NULL_IDX = 0xFFFFFFFF
+NOT_APPLICABLE = 1  # DSX_NOT_APPLICABLE (dsx_filter_probe_cols)
 
 
 class DsxError(RuntimeError):
@@ -571,6 +572,39 @@ class Runtime:
             out.append(DeviceColumn(self, datas[i], valids[i] or None, n,
                                     src.dtype, owner=True))
         return out, n
+
+    def filter_probe_cols(self, table, prog, cols, keyspecs, n, pcols,
+                          bcols):
+        """Fused scan filter + key pack + probe + materialization
+        (dsx_filter_probe_cols) over the unfiltered probe columns `cols`;
+        keyspecs as for keypack, indexing `cols`. Returns ([DeviceColumn]
+        ordered pcols then bcols, n_out), or None when the build keys are
+        not unique (nothing was allocated)."""
+        parr, plen = prog
+        ks = (_KeySpec * len(keyspecs))()
+        for i, (ci, mn, rng, nullable) in enumerate(keyspecs):
+            ks[i].col = ci
+            ks[i].min = mn
+            ks[i].range = rng
+            ks[i].nullable = 1 if nullable else 0
+            ks[i].mode = 0
+        ncols = len(pcols) + len(bcols)
+        datas = (ct.c_void_p * max(ncols, 1))()
+        valids = (ct.c_void_p * max(ncols, 1))()
+        count = ct.c_int64()
+        rc = self.lib.dsx_filter_probe_cols(
+            self.ctx, table, parr, ct.c_int(plen), self._cols_array(cols),
+            ct.c_int(len(cols)), ks, ct.c_int(len(keyspecs)), ct.c_int64(n),
+            self._cols_array(pcols), ct.c_int(len(pcols)),
+            self._cols_array(bcols), ct.c_int(len(bcols)),
+            datas, valids, ct.byref(count))
+        if rc == NOT_APPLICABLE:
+            return None
+        _check(self.lib, rc, "dsx_filter_probe_cols")
+        nr = count.value
+        return [DeviceColumn(self, datas[i], valids[i] or None, nr,
+                             src.dtype, owner=True)
+                for i, src in enumerate(list(pcols) + list(bcols))], nr
 
     def radix_join(self, bcols, n_build, keyspecs_b, keyspecs_p, bpred_prog,
                    pcols, n_probe, join_type, out_specs):

@@ -249,6 +249,26 @@ int dsx_hash_probe_cols(DsxCtx* ctx, DsxHashTable* t, const uint64_t* codes,
                         int force_build_validity, void** out_datas,
                         uint8_t** out_valids, int64_t* out_count);
 
+/* fused scan filter + key pack + probe + materialization for INNER joins
+ * whose build keys are unique (PK-FK): the composition of dsx_filter_cols,
+ * dsx_keypack and dsx_hash_probe_cols over the UNFILTERED probe-side columns,
+ * without the compacted columns, the code column or the slot cache in
+ * between (filter.py:20-45 + join.py:241-246 in one sweep). `cols` serves
+ * both the predicate program (NULL→False) and the key specs (keys[j].col
+ * indexes it; mode 0 only; codes are bit-identical to dsx_keypack's; a row
+ * with a NULL key column never matches). Output rows are in increasing probe
+ * row order; out_datas/out_valids as for dsx_hash_probe_cols.
+ * Returns DSX_NOT_APPLICABLE, with nothing allocated, when the table holds a
+ * duplicate build key — the caller then filters and probes separately. */
+#define DSX_NOT_APPLICABLE 1
+int dsx_filter_probe_cols(DsxCtx* ctx, DsxHashTable* t, const DsxInstr* prog,
+                          int prog_len, const DsxColumn* cols, int ncols,
+                          const DsxKeySpec* keys, int nkeys, int64_t n,
+                          const DsxColumn* pcols, int n_pcols,
+                          const DsxColumn* bcols, int n_bcols,
+                          void** out_datas, uint8_t** out_valids,
+                          int64_t* out_count);
+
 int dsx_hash_unmatched(DsxCtx* ctx, DsxHashTable* t, uint32_t** out_build_idx,
                        int64_t* out_count);
 
