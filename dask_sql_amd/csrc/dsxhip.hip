@@ -67,6 +67,7 @@ struct DsxCtx {
                                      // bit1 probe-emit OOB (DSX_DEBUG)
   bool debug = false;
   void* jit_cache = nullptr;  // JitCacheMap (jit.inc)
+  int64_t fprobe_jit_launches = 0;  // generated j_fprobe_mask launches
   // pinned staging arena for host→HBM ingest (parquet path): pageable
   // hipMemcpy forces an internal staging copy at ~⅓ the PCIe rate;
   // memcpy→pinned + hipMemcpyAsync is the fast path
@@ -2142,6 +2143,20 @@ __global__ void k_fprobe_emit(KeyArg K, ColsArg C, int64_t n,
   }
 }
 
+// the per-shape generated form of k_fprobe_mask (jit_kernels.inc)
+static hipFunction_t fprobe_mask_jit_fn(DsxCtx* c, const ProgArg& P,
+                                        const KeyArg& K, const ColsArg& C,
+                                        int packed);
+static void fprobe_mask_jit_launch(DsxCtx* c, hipFunction_t f, int grid,
+                                   const ColsArg& C, int64_t n,
+                                   const uint64_t* tkeys, int64_t tmask,
+                                   const unsigned int* dup, uint64_t* mask,
+                                   int64_t* block_counts, int64_t* extra);
+
+extern "C" int64_t dsx_fprobe_jit_launches(DsxCtx* c) {
+  return c->fprobe_jit_launches;
+}
+
 extern "C" int dsx_filter_probe_cols(
     DsxCtx* c, DsxHashTable* t, const DsxInstr* prog, int prog_len,
     const DsxColumn* cols, int ncols, const DsxKeySpec* keys, int nkeys,
@@ -2182,12 +2197,20 @@ extern "C" int dsx_filter_probe_cols(
   int64_t h_res[2] = {0, 0};
   if (grid > 0) {
     {
+      // generated kernel first; the interpreter is the fallback (JIT off,
+      // DSX_DISABLE_JIT_FPROBE=1, predicate rejected, hipRTC failure)
+      hipFunction_t fj = fprobe_mask_jit_fn(c, P, K, C, t->packed);
       ProfScope ps(c, "k_fprobe_mask");
-      auto kern = vm_prog_is_lite(prog, prog_len) ? k_fprobe_mask<true>
-                                                  : k_fprobe_mask<false>;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, c->stream, P, K, C,
-                         n, t->keys, t->vals, t->slots - 1, t->packed, t->dup,
-                         mask, block_counts, d_total + 1);
+      if (fj) {
+        fprobe_mask_jit_launch(c, fj, grid, C, n, t->keys, t->slots - 1,
+                               t->dup, mask, block_counts, d_total + 1);
+      } else {
+        auto kern = vm_prog_is_lite(prog, prog_len) ? k_fprobe_mask<true>
+                                                    : k_fprobe_mask<false>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, c->stream, P, K,
+                           C, n, t->keys, t->vals, t->slots - 1, t->packed,
+                           t->dup, mask, block_counts, d_total + 1);
+      }
     }
     hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream,
                        block_counts, grid, d_total);
@@ -3786,6 +3809,94 @@ extern "C" int dsx_jit_pack_source(const DsxKeySpec* keys, int nkeys,
   std::string src = os.str();
   if ((int64_t)src.size() + 1 > cap) return -2;
   memcpy(buf, src.c_str(), src.size() + 1);
+  return 0;
+}
+
+// dsx_jit_fprobe_source — TEST INFRASTRUCTURE (like dsx_jit_expr_source):
+// the generated filter-probe mask kernel's full source for a shape, exactly
+// the text dsx_filter_probe_cols compiles. Only the PRESENCE of validity
+// buffers enters; pointers, n and the table mask are kernel arguments.
+// words <= 0 selects the shipped value. Host-only: no HIP calls.
+// Returns 0; -1 when the generator rejects the predicate (the caller's
+// interpreter fallback), -2 when buf is too small, -3 on a malformed spec.
+extern "C" int dsx_jit_fprobe_source(const DsxInstr* prog, int prog_len,
+                                     const DsxKeySpec* keys, int nkeys,
+                                     const int32_t* dtypes,
+                                     const uint8_t* has_validity, int ncols,
+                                     int packed, int words, char* buf,
+                                     int64_t cap) {
+  if (prog_len < 0 || prog_len > DSX_MAX_PROG || nkeys <= 0 ||
+      nkeys > DSX_MAX_KEYS || ncols < 0 || ncols > DSX_MAX_COLS || words > 8)
+    return -3;
+  ProgArg P{};
+  memcpy(P.ins, prog, prog_len * sizeof(DsxInstr));
+  P.len = prog_len;
+  KeyArg K{};
+  if (make_keyarg(keys, nkeys, K)) return -3;
+  for (int j = 0; j < nkeys; j++)
+    if (keys[j].mode != 0 || keys[j].col < 0 || keys[j].col >= ncols)
+      return -3;
+  ColsArg C{};
+  C.ncols = ncols;
+  for (int i = 0; i < ncols; i++) {
+    C.dtype[i] = dtypes[i];
+    C.validity[i] = has_validity[i] ? (const uint8_t*)1 : nullptr;
+  }
+  std::string src =
+      jit_fprobe_source(C, K, P, packed != 0,
+                        words <= 0 ? DSX_FPROBE_JIT_WORDS : words);
+  if (src.empty()) return -1;
+  if ((int64_t)src.size() + 1 > cap) return -2;
+  memcpy(buf, src.c_str(), src.size() + 1);
+  return 0;
+}
+
+// dsx_jit_compile_check — TEST INFRASTRUCTURE: hipRTC-compile a generated
+// source for gfx950 with the options the runtime uses. Needs no GPU (nothing
+// is loaded). Returns 0, or 1 with the compiler log on stderr.
+extern "C" int dsx_jit_compile_check(const char* src) {
+  hiprtcProgram prog;
+  if (hiprtcCreateProgram(&prog, src, "dsx_check.cu", 0, nullptr, nullptr) !=
+      HIPRTC_SUCCESS)
+    return 1;
+  const char* opts[] = {"-O3", "--offload-arch=gfx950", "-std=c++17",
+                        "-munsafe-fp-atomics"};
+  hiprtcResult rc = hiprtcCompileProgram(prog, 4, opts);
+  if (rc != HIPRTC_SUCCESS) {
+    size_t lsz = 0;
+    hiprtcGetProgramLogSize(prog, &lsz);
+    std::string log(lsz, '\0');
+    if (lsz) hiprtcGetProgramLog(prog, &log[0]);
+    fprintf(stderr, "[dsxhip] JIT compile check FAILED:\n%s\n", log.c_str());
+  }
+  hiprtcDestroyProgram(&prog);
+  return rc == HIPRTC_SUCCESS ? 0 : 1;
+}
+
+// dsx_jit_fprobe_selftest — compile-check the generated filter-probe kernel
+// for the Q3 probe shapes (i32 date vs constant, one i64 key, packed) and an
+// unpacked composite with a nullable key, at R = 1, 2, 4 and 8, WITHOUT a GPU
+// (like dsx_jit_selftest). Returns 0, or 100·(shape + 1) + R of the first
+// failure.
+extern "C" int dsx_jit_fprobe_selftest(void) {
+  DsxInstr pred[3] = {{DSX_OP_COL, 0, 0}, {DSX_OP_LIT_I64, 0, 9204},
+                      {DSX_OP_GT_I64, 0, 0}};
+  for (int shape = 0; shape < 2; shape++) {
+    int32_t dtypes[3] = {DSX_I32, DSX_I64, DSX_I32};
+    uint8_t hv[3] = {0, 0, (uint8_t)shape};
+    DsxKeySpec keys[2]{};
+    keys[0].col = 1;
+    keys[0].range = shape ? (int64_t)1 << 40 : 60'000'000;
+    keys[1].col = 2;
+    keys[1].range = 1000;
+    keys[1].nullable = 1;
+    static char buf[1 << 17];
+    for (int R : {1, 2, 4, 8}) {
+      int rc = dsx_jit_fprobe_source(pred, 3, keys, shape ? 2 : 1, dtypes, hv,
+                                     3, shape ? 0 : 1, R, buf, sizeof buf);
+      if (rc || dsx_jit_compile_check(buf)) return 100 * (shape + 1) + R;
+    }
+  }
   return 0;
 }
 

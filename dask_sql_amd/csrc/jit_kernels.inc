@@ -685,3 +685,151 @@ static JitEntry* jit_source_entry(DsxCtx* c, const std::string& src) {
   }
   return e;
 }
+
+// ---------------------------------------------------------------------------
+// j_fprobe_mask — the filter-probe mask pass (k_fprobe_mask's contract,
+// dsxhip.hip) specialized per query shape: predicate, key pack, key-validity
+// presence, table layout and R (64-row words per wave iteration) are inlined;
+// pointers, n and tmask are kernel arguments so the source text — the cache
+// key — is stable from call to call.
+//
+// The interpreter kernel waits for every load before it issues the next
+// (validity → predicate column → key → first slot → chain: five dependent
+// round trips per word) and spends ~11 500 instructions on its switches.
+// Here a wave takes R consecutive words and the body runs in phases so that
+// independent loads are in flight together:
+//   A  every predicate/validity/key load of the R words, unconditionally
+//      (the row index is clamped on the tail — a per-word "load or not"
+//      would make the compiler branch and wait per word);
+//   B  predicates, codes, hashes;
+//   C  the R first-slot loads back to back (rows that failed the predicate
+//      read slot 0: one broadcast line, no branch);
+//   D  chain continuation, live lanes only, one word's chain after another.
+// Load factor ≤ 0.5, so an EMPTY slot always ends a chain.
+//
+// Measured on Q3 SF10 (DESIGN.md §8 Round 4): the specialization halves the
+// pass; every R above 1 is slower than R = 1 (as was a lock-step chain walk
+// with R loads per round), so R = 1 ships and DSX_FPROBE_R re-measures.
+// ---------------------------------------------------------------------------
+#define DSX_FPROBE_JIT_WORDS 1  // shipped R
+
+static std::string jit_fprobe_source(const ColsArg& C, const KeyArg& K,
+                                     const ProgArg& P, bool packed, int R) {
+  if (R < 1 || R > 8 || K.nkeys < 1) return "";
+  std::ostringstream os;
+  os << JIT_PRELUDE;
+  char k;
+  if (!jit_emit_fn(os, "eval_pred", P.ins, P.len, &C, &k)) return "";
+  jit_emit_pack(os, K, &C);
+  // NULL key never matches: every key column that carries a validity buffer
+  os << "__device__ __forceinline__ bool jit_key_valid(const ColsArg& C, "
+        "i64 r) {\n  bool ok = true;\n";
+  for (int j = 0; j < K.nkeys; j++)
+    if (C.validity[K.k[j].col])
+      os << "  ok = ok & (C.validity[" << K.k[j].col << "][r] != 0);\n";
+  os << "  return ok;\n}\n";
+  const char* match = packed ? "(k[j] >> 32) == code[j]" : "k[j] == code[j]";
+  os << "#define R " << R << "\n#define EMPTY_KEY 0xFFFFFFFFFFFFFFFFull\n"
+     << "#define MATCH(j) (" << match << ")\n";
+  os << R"(
+extern "C" __global__ void __launch_bounds__(BLOCK) j_fprobe_mask(
+    ColsArg C, i64 n, const u64* __restrict__ tkeys, i64 tmask,
+    const u32* __restrict__ dup, u64* __restrict__ mask,
+    i64* __restrict__ block_counts, i64* __restrict__ extra) {
+  i64 lo, hi; block_range(n, 64, lo, hi);
+  __shared__ u64 s_count;
+  if (threadIdx.x == 0) {
+    s_count = 0;
+    if (blockIdx.x == 0) extra[0] = (i64)*dup;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const i64 w0 = (lo + 63) / 64, w1 = (hi + 63) / 64;  // lo == hi: no words
+  i64 local = 0;
+  for (i64 wb = w0 + (i64)wid * R; wb < w1; wb += (BLOCK / 64) * R) {
+    bool alive[R]; u64 code[R]; i64 s[R]; u64 k[R];
+    // A: all column loads of the R words, in one branch-free block
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      i64 r = (wb + j) * 64 + lane;
+      i64 rc = r < n ? r : n - 1;  // clamped: the loads stay unconditional
+      i64 pv; bool ok = eval_pred(C, rc, pv);
+      bool kv = jit_key_valid(C, rc);
+      code[j] = jit_pack(C, rc);
+      alive[j] = (r < hi) & ok & (pv != 0) & kv;  // NULL predicate: false
+    }
+    // B: hashes (kept apart from A: the compiler branches around the 64-bit
+    // multiplies of a word with no live row, and a branch in A would make
+    // each word's loads wait for the previous word's)
+#pragma unroll
+    for (int j = 0; j < R; j++)
+      s[j] = alive[j] ? (i64)(mix64(code[j]) & (u64)tmask) : 0;
+    // C: first slots, back to back
+#pragma unroll
+    for (int j = 0; j < R; j++) k[j] = tkeys[s[j]];
+    bool hit[R];
+    // D: the rest of each chain, one word after another
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      hit[j] = false;
+      bool go = alive[j];
+      while (go) {
+        if (k[j] == EMPTY_KEY) break;
+        if (MATCH(j)) { hit[j] = true; break; }
+        s[j] = (s[j] + 1) & tmask;
+        k[j] = tkeys[s[j]];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      u64 m = __builtin_amdgcn_ballot_w64(hit[j]);
+      if (lane == 0 && wb + j < w1) {
+        mask[wb + j] = m;
+        local += __builtin_popcountll(m);
+      }
+    }
+  }
+  if (lane == 0) atomicAdd(&s_count, (u64)local);
+  __syncthreads();
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = (i64)s_count;
+}
+)";
+  return os.str();
+}
+
+// read per call, so one process can run both variants
+static bool jit_fprobe_enabled() {
+  const char* e = getenv("DSX_DISABLE_JIT_FPROBE");
+  return !(e && *e && strcmp(e, "0") != 0);
+}
+
+// measurement knob behind the Round 4 comparison: DSX_FPROBE_R = 1..8 words
+// per wave iteration; unset or out of range, the shipped value holds
+static int jit_fprobe_words() {
+  const char* e = getenv("DSX_FPROBE_R");
+  int v = e ? atoi(e) : 0;
+  return v < 1 || v > 8 ? DSX_FPROBE_JIT_WORDS : v;
+}
+
+// the generated mask kernel for this shape, or nullptr: JIT disabled, the
+// generator rejects the predicate, or hipRTC failed (negative-cached)
+static hipFunction_t fprobe_mask_jit_fn(DsxCtx* c, const ProgArg& P,
+                                        const KeyArg& K, const ColsArg& C,
+                                        int packed) {
+  if (!jit_enabled() || !jit_fprobe_enabled()) return nullptr;
+  JitEntry* je = jit_source_entry(
+      c, jit_fprobe_source(C, K, P, packed != 0, jit_fprobe_words()));
+  return je ? jit_fn(c, je, "j_fprobe_mask") : nullptr;
+}
+
+static void fprobe_mask_jit_launch(DsxCtx* c, hipFunction_t f, int grid,
+                                   const ColsArg& C, int64_t n,
+                                   const uint64_t* tkeys, int64_t tmask,
+                                   const unsigned int* dup, uint64_t* mask,
+                                   int64_t* block_counts, int64_t* extra) {
+  ColsArg Ca = C;
+  void* args[] = {&Ca, &n, &tkeys, &tmask, &dup, &mask, &block_counts, &extra};
+  hipModuleLaunchKernel(f, grid, 1, 1, BLOCK, 1, 1, 0, c->stream, args,
+                        nullptr);
+  c->fprobe_jit_launches++;
+}

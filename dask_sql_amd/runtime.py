@@ -44,6 +44,9 @@ AGG_MIN_F64, AGG_MAX_F64, AGG_MIN_I64, AGG_MAX_I64 = 3, 4, 5, 6
 JOIN_INNER, JOIN_LEFT, JOIN_LEFTSEMI, JOIN_LEFTANTI = 0, 1, 2, 3
 NULL_IDX = 0xFFFFFFFF
 NOT_APPLICABLE = 1  # DSX_NOT_APPLICABLE (dsx_filter_probe_cols)
+# 64-row words per wave iteration of the generated filter-probe mask kernel
+# (DSX_FPROBE_JIT_WORDS, csrc/jit_kernels.inc)
+FPROBE_JIT_WORDS = 1
 
 
 class DsxError(RuntimeError):
@@ -605,6 +608,15 @@ class Runtime:
         return [DeviceColumn(self, datas[i], valids[i] or None, nr,
                              src.dtype, owner=True)
                 for i, src in enumerate(list(pcols) + list(bcols))], nr
+
+    def fprobe_jit_launches(self) -> int:
+        """Launches so far of the per-shape generated mask kernel of
+        filter_probe_cols (dsx_fprobe_jit_launches). A call that leaves the
+        count unchanged ran the interpreter kernel (DSX_DISABLE_JIT,
+        DSX_DISABLE_JIT_FPROBE=1, a rejected predicate, a hipRTC failure) or
+        had no rows."""
+        self.lib.dsx_fprobe_jit_launches.restype = ct.c_int64
+        return int(self.lib.dsx_fprobe_jit_launches(self.ctx))
 
     def radix_join(self, bcols, n_build, keyspecs_b, keyspecs_p, bpred_prog,
                    pcols, n_probe, join_type, out_specs):

@@ -269,6 +269,15 @@ int dsx_filter_probe_cols(DsxCtx* ctx, DsxHashTable* t, const DsxInstr* prog,
                           void** out_datas, uint8_t** out_valids,
                           int64_t* out_count);
 
+/* The mask pass of dsx_filter_probe_cols runs a kernel generated per query
+ * shape (hipRTC; predicate, key pack and table layout inlined, a word's
+ * column loads in flight together) and falls
+ * back to the interpreter kernel when DSX_DISABLE_JIT or
+ * DSX_DISABLE_JIT_FPROBE=1 is set (the latter is read on every call), the
+ * generator rejects the predicate, or hipRTC fails. Both fill the same mask.
+ * This counts the launches of the generated kernel on `ctx` so far. */
+int64_t dsx_fprobe_jit_launches(DsxCtx* ctx);
+
 int dsx_hash_unmatched(DsxCtx* ctx, DsxHashTable* t, uint32_t** out_build_idx,
                        int64_t* out_count);
 
@@ -391,6 +400,27 @@ int dsx_jit_expr_source(const DsxInstr* prog, int prog_len,
 int dsx_jit_pack_source(const DsxKeySpec* keys, int nkeys,
                         const int32_t* dtypes, const uint8_t* has_validity,
                         int ncols, char* buf, int64_t cap);
+
+/* TEST INFRASTRUCTURE: the full source of the generated filter-probe mask
+ * kernel for a shape (host-only, no GPU). has_validity gives only the
+ * PRESENCE of validity buffers; pointers, n and the table mask are kernel
+ * arguments and never enter the text. packed: table layout; words: 64-row
+ * words per wave iteration (1..8, <= 0 for the shipped value). Returns 0;
+ * -1 when the generator rejects the predicate (callers fall back to the
+ * interpreter kernel), -2 when buf is too small, -3 on a malformed spec. */
+int dsx_jit_fprobe_source(const DsxInstr* prog, int prog_len,
+                          const DsxKeySpec* keys, int nkeys,
+                          const int32_t* dtypes, const uint8_t* has_validity,
+                          int ncols, int packed, int words, char* buf,
+                          int64_t cap);
+
+/* TEST INFRASTRUCTURE: hipRTC-compile `src` for gfx950 with the runtime's
+ * options; needs no GPU. Returns 0, or 1 with the log on stderr. */
+int dsx_jit_compile_check(const char* src);
+
+/* TEST INFRASTRUCTURE: compile-check the generated filter-probe kernel for
+ * representative shapes at every unroll factor; 0 on success. */
+int dsx_jit_fprobe_selftest(void);
 
 #ifdef __cplusplus
 }
