@@ -3754,6 +3754,7 @@ void jit_cache_destroy(DsxCtx* c) {
 #include "radix_join.inc"
 #include "sort.inc"
 #include "window.inc"
+#include "window_rows.inc"
 
 // ---------------------------------------------------------------------------
 // dsx_jit_expr_source — TEST INFRASTRUCTURE: emit the JIT expression

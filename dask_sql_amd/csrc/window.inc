@@ -19,6 +19,7 @@ enum DsxWinFunc {
   DSX_WIN_LAG = 3, DSX_WIN_LEAD = 4, DSX_WIN_FIRST = 5,
   DSX_WIN_RSUM = 6, DSX_WIN_RCOUNT = 7, DSX_WIN_RMIN = 8, DSX_WIN_RMAX = 9,
   DSX_WIN_RAVG = 10,
+  DSX_WIN_LAST = 11,  // explicit ROWS frames only (window_rows.inc)
 };
 
 __global__ void k_win_mark(const uint64_t* codes, int64_t n, uint8_t* out) {

@@ -2648,7 +2648,16 @@ class DaskWindowPlugin(BaseRelPlugin):
       the REFERENCE computes these in pandas per partition
       (window.py:266-427 map_on_each_group); we restate the same pandas
       computation on host over the key columns, then upload the one result
-      column. Parity-first; a device sort is a round-2+ widening."""
+      column. Parity-first; a device sort is a round-2+ widening;
+    - explicit ROWS frames (SUM/COUNT/AVG/MIN/MAX/FIRST_VALUE/LAST_VALUE
+      over ROWS BETWEEN … AND … / ROWS k PRECEDING): device-side through
+      _device_rows → dsx_window_rows (LDS tile pass for narrow bounded
+      frames, per-partition scans + prefix differences otherwise). They
+      fall back to the host rolling restatement (_frame_apply) when
+      DSX_DISABLE_DEVWINDOW is set, an order key is explicitly NULLS
+      FIRST, a key is not an integer kind or does not pack, sort_perm
+      refuses, the value column is dictionary-encoded, or a bounded
+      MIN/MAX frame is wider than window_frames.WIN_ROWS_TILE_MAXW."""
 
     class_name = "Window"
 
@@ -2691,8 +2700,13 @@ class DaskWindowPlugin(BaseRelPlugin):
                 out.dictionary = src.dictionary
             return out
         if getattr(spec, "frame", None) is not None:
-            # explicit ROWS frames run the reference's own rolling pandas
-            # computation host-side (window.py:145-198 map_on_each_group)
+            # explicit ROWS frames: device tile / scan kernels
+            # (dsx_window_rows); shapes they do not cover run the
+            # reference's own rolling pandas computation host-side
+            # (window.py:145-198 map_on_each_group)
+            col = self._device_rows(runtime, cols, n, spec)
+            if col is not None:
+                return col
             return self._host_ordered(runtime, cols, n, spec)
         device_ok = (spec.func in self._AGGS and not spec.order_idx
                      and spec.part_idx  # OVER () = whole-table agg → host
@@ -2760,18 +2774,12 @@ class DaskWindowPlugin(BaseRelPlugin):
         # frame — realign positionally
         return pd.Series(res.to_numpy(), index=df.index)
 
-    def _device_ordered(self, runtime, cols, n, spec):
-        """Device ordered window frames (VERDICT r1 #5): sort permutation
-        over (partition, order) keys → boundary starts → dsx_window_ordered
-        (binary-search ranks / shifts; per-partition running scans with
-        peer broadcast). Mirrors _host_ordered's pandas semantics exactly
-        (na_position="last" on order keys, partitions keep NULL groups).
-        Returns None on unsupported shapes → host fallback."""
-        import os as _os
-        if _os.environ.get("DSX_DISABLE_DEVWINDOW") or n == 0:
-            return None
-        if spec.func not in runtime.WIN_FUNCS:
-            return None
+    def _device_sort_keys(self, runtime, cols, n, spec, need_full=True):
+        """Shared front half of the device window paths: the sort
+        permutation over (partition, order) keys plus the partition codes
+        (and, with need_full, the partition+order peer codes) gathered into
+        sorted order. None when a key is not an integer kind, the key space
+        does not pack, or sort_perm refuses → host fallback."""
         work = list(cols)
 
         def key_of(i, want_rank):
@@ -2839,11 +2847,31 @@ class DaskWindowPlugin(BaseRelPlugin):
         fspecs = pspecs + [spec_of(*o, True) for o in order]
         try:
             pcodes = packed(pspecs)
-            fcodes = packed(fspecs) if order else pcodes
+            fcodes = packed(fspecs) if order and need_full \
+                else pcodes
         except Exception:
             return None  # key space overflow etc → host
         ps = runtime.gather(pcodes, perm.data, n)
-        fs = runtime.gather(fcodes, perm.data, n) if order else ps
+        fs = runtime.gather(fcodes, perm.data, n) \
+            if order and need_full else ps
+        return perm, ps, fs
+
+    def _device_ordered(self, runtime, cols, n, spec):
+        """Device ordered window frames (VERDICT r1 #5): sort permutation
+        over (partition, order) keys → boundary starts → dsx_window_ordered
+        (binary-search ranks / shifts; per-partition running scans with
+        peer broadcast). Mirrors _host_ordered's pandas semantics exactly
+        (na_position="last" on order keys, partitions keep NULL groups).
+        Returns None on unsupported shapes → host fallback."""
+        import os as _os
+        if _os.environ.get("DSX_DISABLE_DEVWINDOW") or n == 0:
+            return None
+        if spec.func not in runtime.WIN_FUNCS:
+            return None
+        keys = self._device_sort_keys(runtime, cols, n, spec)
+        if keys is None:
+            return None
+        perm, ps, fs = keys
 
         v_col = cols[spec.arg_idx] if spec.arg_idx is not None else None
         func = spec.func
@@ -2888,6 +2916,47 @@ class DaskWindowPlugin(BaseRelPlugin):
                                      spec.offset, default_bits, has_def,
                                      out_dtype, want_valid)
         col._keep_alive = (perm, ps, fs, v_col)
+        return col
+
+    def _device_rows(self, runtime, cols, n, spec):
+        """Device explicit ROWS frames (dsx_window_rows): the sort front
+        half of _device_ordered, then window_frames.lower_rows_frame picks
+        the LDS tile pass or the per-partition scans. Reproduces
+        _frame_apply: an empty frame is NULL for every function (COUNT
+        too), FIRST/LAST return the boundary row as is. Returns None on
+        unsupported shapes → host fallback."""
+        import os as _os
+        from dask_sql_amd.physical import window_frames as wf
+        if _os.environ.get("DSX_DISABLE_DEVWINDOW") or n == 0:
+            return None
+        func = spec.func
+        if func not in runtime.WIN_ROWS_FUNCS:
+            return None
+        lo_off, hi_off, strategy = wf.lower_rows_frame(func, spec.frame)
+        if strategy == "host":
+            return None
+        v_col = cols[spec.arg_idx] if spec.arg_idx is not None else None
+        if v_col is None and func != "count":
+            return None
+        if v_col is not None and getattr(v_col, "dictionary",
+                                         None) is not None:
+            return None  # string payload: host
+        keys = self._device_sort_keys(runtime, cols, n, spec,
+                                      need_full=False)
+        if keys is None:
+            return None
+        perm, ps, _fs = keys
+        is_big = spec.out_type is not None and \
+            spec.out_type.getSqlType() == "BIGINT"
+        kind, want_valid = wf.frame_out_dtype(
+            func, lo_off, hi_off, is_big,
+            v_col is not None and bool(v_col.validity))
+        out_dtype = {"i64": rt.I64, "f64": rt.F64}.get(kind)
+        if out_dtype is None:
+            out_dtype = v_col.dtype
+        col = runtime.window_rows(perm, n, ps, func, v_col, lo_off, hi_off,
+                                  out_dtype, want_valid)
+        col._keep_alive = (perm, ps, v_col)
         return col
 
     def _device_agg(self, runtime, cols, n, spec):

@@ -718,6 +718,36 @@ class Runtime:
         return DeviceColumn(self, d.value, vv.value or None, n, out_dtype,
                             owner=True)
 
+    # dsx_window_rows func ids: the aggregate ids above + FIRST and LAST
+    WIN_ROWS_FUNCS = {"sum": 6, "count": 7, "min": 8, "max": 9, "avg": 10,
+                      "first_value": 5, "last_value": 11}
+
+    def window_rows(self, perm, n, pcode_sorted, func, v_col, lo_off, hi_off,
+                    out_dtype, want_valid):
+        """Device explicit ROWS frame (dsx_window_rows). lo_off / hi_off are
+        row offsets relative to the current sorted row (PRECEDING negative),
+        None = unbounded side."""
+        d = ct.c_void_p()
+        vv = ct.c_void_p()
+        vstruct = v_col.c_struct() if v_col is not None else None
+        _check(
+            self.lib,
+            self.lib.dsx_window_rows(
+                self.ctx, ct.c_void_p(perm.data), ct.c_int64(n),
+                ct.c_void_p(pcode_sorted.data),
+                ct.c_int(self.WIN_ROWS_FUNCS[func]),
+                ct.byref(vstruct) if vstruct is not None else None,
+                ct.c_int(1 if lo_off is None else 0),
+                ct.c_int64(0 if lo_off is None else lo_off),
+                ct.c_int(1 if hi_off is None else 0),
+                ct.c_int64(0 if hi_off is None else hi_off),
+                ct.c_int(out_dtype), ct.byref(d), ct.byref(vv),
+                ct.c_int(1 if want_valid else 0)),
+            "dsx_window_rows",
+        )
+        return DeviceColumn(self, d.value, vv.value or None, n, out_dtype,
+                            owner=True)
+
     def hash_table_free(self, table):
         self.lib.dsx_hash_table_free(table)
 

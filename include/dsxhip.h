@@ -325,6 +325,42 @@ int dsx_window_ordered(DsxCtx* ctx, const uint32_t* perm, int64_t n,
                        int64_t default_bits, int has_default, int out_dtype,
                        void** out_data, uint8_t** out_valid, int want_valid);
 
+/* Width thresholds of the ROWS-frame paths below (starting values, not
+ * tuned): a bounded frame of W = hi_off - lo_off + 1 rows is reduced
+ * directly out of an LDS tile when W <= DIRECT_MAXW (SUM/COUNT/AVG) or
+ * W <= TILE_MAXW (MIN/MAX). dsx_window_rows_limits reports them to the
+ * caller that picks the strategy. */
+#define DSX_WIN_ROWS_DIRECT_MAXW 64
+#define DSX_WIN_ROWS_TILE_MAXW 1024
+int dsx_window_rows_limits(int* direct_maxw, int* tile_maxw);
+
+/* Device explicit ROWS frames (reference rel/logical/window.py:145-198 —
+ * map_on_each_group's expanding / rolling / BaseIndexer chain per sorted
+ * partition). Same inputs as dsx_window_ordered minus the peer codes. The
+ * frame of sorted row i in partition [p0, p1) is [max(p0, i + lo_off),
+ * min(p1 - 1, i + hi_off)], a side dropping its offset when unbounded;
+ * PRECEDING offsets are negative, CURRENT ROW is 0. An EMPTY frame yields
+ * NULL for every function, COUNT included. func = DsxWinFunc SUM/COUNT/MIN/
+ * MAX/AVG (6..10), FIRST_VALUE (5) or LAST_VALUE (11):
+ *  - bounded frames up to the widths above: one LDS tile pass
+ *    (k_win_rows_tile);
+ *  - wider SUM/COUNT/AVG and any unbounded side: three-phase per-partition
+ *    scan (k_win_segscan_tile/_carry/_apply; reverse for MIN/MAX with only
+ *    the high side unbounded) + k_win_rows_prefix;
+ *  - FIRST/LAST: positional bit copy in the value dtype (out_dtype must
+ *    equal it), NULL when the boundary row is NULL;
+ *  - bounded MIN/MAX wider than DSX_WIN_ROWS_TILE_MAXW: returns -7, the
+ *    caller keeps those on the host.
+ * Aggregates accumulate in f64 and write out_dtype I64 or F64 (COUNT(*) =
+ * value_or_null NULL). Results land in original row order. On failure
+ * nothing stays allocated and *out_data / *out_valid are NULL. */
+int dsx_window_rows(DsxCtx* ctx, const uint32_t* perm, int64_t n,
+                    const uint64_t* pcode_sorted, int func,
+                    const DsxColumn* value_or_null, int lo_unbounded,
+                    int64_t lo_off, int hi_unbounded, int64_t hi_off,
+                    int out_dtype, void** out_data, uint8_t** out_valid,
+                    int want_valid);
+
 /* ---- hash groupby-aggregate --------------------------------------------- */
 
 enum DsxAggOp {  /* reference AGGREGATION_MAPPING aggregate.py:117-231 subset:
