@@ -3753,6 +3753,7 @@ void jit_cache_destroy(DsxCtx* c) {
 
 #include "radix_join.inc"
 #include "sort.inc"
+#include "radix_sort.inc"
 #include "window.inc"
 #include "window_rows.inc"
 

@@ -687,6 +687,36 @@ class Runtime:
         _check(self.lib, rc, "dsx_sort_perm")
         return DeviceColumn(self, perm.value, None, n, I32, owner=True)
 
+    def sort_word(self, cols, keyspecs, n, perm_in=None):
+        """Stable device sort of a row-id sequence by ONE 64-bit order word
+        (dsx_sort_word, LSD radix). `cols` are the word's own key columns,
+        keyspecs = (col, min, range, nullable, mode) as for sort_perm, or a
+        single float key with mode bit 8. perm_in: DeviceColumn of u32 row
+        ids to reorder (None = identity). Chained least significant word
+        first it sorts composite keys of any width. Returns a DeviceColumn
+        of u32 row ids or None (-3/-4: unsupported → host)."""
+        nk = len(keyspecs)
+        ks = (_KeySpec * max(nk, 1))()
+        for i, spec in enumerate(keyspecs):
+            ks[i].col = spec[0]
+            ks[i].min = spec[1]
+            ks[i].range = spec[2]
+            ks[i].nullable = 1 if spec[3] else 0
+            ks[i].mode = spec[4]
+        if perm_in is not None and perm_in.len != n:
+            raise DsxError(f"sort_word: perm_in has {perm_in.len} ids, "
+                           f"expected {n}")
+        perm = ct.c_void_p()
+        rc = self.lib.dsx_sort_word(
+            self.ctx, self._cols_array(cols), ct.c_int(len(cols)), ks,
+            ct.c_int(nk), ct.c_int64(n),
+            ct.c_void_p(perm_in.data) if perm_in is not None else None,
+            ct.byref(perm))
+        if rc in (-3, -4):
+            return None
+        _check(self.lib, rc, "dsx_sort_word")
+        return DeviceColumn(self, perm.value, None, n, I32, owner=True)
+
     WIN_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "lag": 3,
                  "lead": 4, "first_value": 5, "sum": 6, "count": 7,
                  "min": 8, "max": 9, "avg": 10}

@@ -194,7 +194,10 @@ typedef struct DsxKeySpec {
   int32_t mode;       /* 0 = radix pack; 1 = f64 bit-pattern (must be the
                          ONLY key): code = canonical_bits(x)+1, NaN and NULL
                          share code 0 — pandas groups NaN keys together under
-                         dropna=False (aggregate.py:575-577) */
+                         dropna=False (aggregate.py:575-577).
+                         ORDER BY entries (dsx_sort_perm, dsx_sort_word):
+                         bit1 (2) = DESC, bit2 (4) = NULLS LAST, bit3 (8) =
+                         float key, a word of its own (dsx_sort_word only) */
 } DsxKeySpec;
 int dsx_keypack(DsxCtx* ctx, const DsxColumn* cols, int ncols,
                 const DsxKeySpec* keys, int nkeys, int64_t n,
@@ -310,6 +313,32 @@ int dsx_radix_join(DsxCtx* ctx, const DsxColumn* build_cols, int n_build_cols,
  * row permutation; -6 on skew (caller sorts on host). */
 int dsx_sort_perm(DsxCtx* ctx, const DsxColumn* cols, int ncols,
                   const DsxKeySpec* keys, int nkeys, int64_t n,
+                  uint32_t** out_perm);
+
+/* Stable LSD radix sort of a row-id sequence by ONE 64-bit order "word"
+ * (reference physical/utils/sort.py:36-60 — `df.sort_values(kind=
+ * "mergesort")` applied key by key from the last ORDER BY key to the
+ * first). Sorts perm_in[0..n) (NULL = identity 0..n-1) stably by the word
+ * code of the row each entry names and returns the new permutation
+ * (library-allocated u32[n]; free with dsx_free). Stability makes a
+ * composite key of any width a chain of calls, least significant word
+ * first, each call taking the previous result as perm_in. A word is
+ *  - up to DSX_MAX_KEYS integer-kind keys, packed exactly as dsx_sort_perm
+ *    packs them (mode bit1 = DESC, bit2 = NULLS LAST, keys REVERSED, key
+ *    space <= 2^62 else -4), or
+ *  - ONE float key (F64 or F32 column), DsxKeySpec mode bit3 (value 8),
+ *    optionally with bits 1 and 2; min/range/nullable are ignored. Its code
+ *    is the inline function of csrc/sort_code.h: NULL and NaN share the null
+ *    slot on the na_position side, -0.0 ties with +0.0.
+ * `cols` holds only the word's own key columns (keys[j].col indexes it), so
+ * the table's width does not matter. Digits (bytes) of the code that are
+ * constant across all rows are skipped. Never returns -6: no input
+ * distribution overloads it. -3 on a malformed spec or n > 0xFFFFFFFE. On
+ * failure nothing stays allocated and *out_perm is NULL. DSX_RSORT_GRID=<g>
+ * (read per call) caps the launch grid — test knob. */
+int dsx_sort_word(DsxCtx* ctx, const DsxColumn* cols, int ncols,
+                  const DsxKeySpec* keys, int nkeys, int64_t n,
+                  const uint32_t* perm_in /* nullable = identity */,
                   uint32_t** out_perm);
 
 /* Device ordered window frames (reference rel/logical/window.py:212-428):
