@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/dsxhip.h"
+#include "join_filter.h"
 
 #define BLOCK 256
 #define WAVES_PER_BLOCK (BLOCK / 64)
@@ -68,6 +69,7 @@ struct DsxCtx {
   bool debug = false;
   void* jit_cache = nullptr;  // JitCacheMap (jit.inc)
   int64_t fprobe_jit_launches = 0;  // generated j_fprobe_mask launches
+  int64_t join_filter_builds[3] = {0, 0, 0};  // filtered builds per mode
   // pinned staging arena for host→HBM ingest (parquet path): pageable
   // hipMemcpy forces an internal staging copy at ~⅓ the PCIe rate;
   // memcpy→pinned + hipMemcpyAsync is the fast path
@@ -1442,18 +1444,38 @@ struct DsxHashTable {
   int packed = 0;             // codes < 2^32-1 → one 8-B entry per slot,
                               // single random read per probe
   unsigned int* dup = nullptr;  // device flag: any duplicate build key
+  // key-membership filter (join_filter.h), consulted by the filter-probe mask
+  // pass only: most probes of a selective join end on an EMPTY slot, and a
+  // filter small enough to stay in L2 answers those without a table line
+  uint32_t* filter = nullptr;
+  int filter_mode = DSX_JF_NONE;
+  uint64_t filter_arg = 0;    // exact: code_max; hashed: word count - 1
+  int64_t filter_bytes = 0;
   DsxCtx* ctx = nullptr;
 };
 
 __global__ void k_hash_build(const uint64_t* codes, const uint8_t* validity,
                              int64_t n, uint64_t* tkeys, uint32_t* tvals,
-                             int64_t mask, int packed, unsigned int* dup) {
+                             int64_t mask, int packed, unsigned int* dup,
+                             uint32_t* filter, int filter_mode,
+                             uint64_t filter_arg) {
   int64_t lo, hi;
   block_range(n, 1, lo, hi);
   bool saw_dup = false;
   for (int64_t r = lo + threadIdx.x; r < hi; r += BLOCK) {
     if (validity && !validity[r]) continue;  // NULL-key drop (join.py:202-213)
     uint64_t cde = codes[r];
+    if (filter_mode == DSX_JF_EXACT) {
+      // a code past code_max cannot come from a caller that keeps its own
+      // bound; it is left out of the bitmap rather than written past it, and
+      // the probe side treats such codes as misses
+      if (cde <= filter_arg)
+        atomicOr(&filter[dsx_jf_exact_word(cde)], dsx_jf_exact_bit(cde));
+    } else if (filter_mode == DSX_JF_HASHED) {
+      uint64_t h = dsx_jf_mix64(cde);
+      atomicOr(&filter[dsx_jf_hashed_word(h, filter_arg)],
+               dsx_jf_hashed_bits(h));
+    }
     uint64_t entry = packed ? ((cde << 32) | (uint64_t)(uint32_t)r) : cde;
     int64_t s = (int64_t)(mix64(cde) & mask);
     while (true) {
@@ -1474,9 +1496,46 @@ __global__ void k_hash_build(const uint64_t* codes, const uint8_t* validity,
   if (saw_dup) atomicOr(dup, 1u);
 }
 
-extern "C" int dsx_hash_build(DsxCtx* c, const uint64_t* codes,
-                              const uint8_t* validity, int64_t n,
-                              uint64_t code_max, DsxHashTable** out) {
+// read per call, so one process can run both variants (A/B, tests)
+static bool join_filter_enabled() {
+  const char* e = getenv("DSX_DISABLE_JOINFILTER");
+  return !(e && *e && strcmp(e, "0") != 0);
+}
+
+// picks the filter of a table of n build rows: exact when the table is packed
+// and code_max + 1 bits fit under the byte cap; else hashed at the next power
+// of two >= DSX_JF_BITS_PER_KEY bits per row, clamped to the cap; no filter
+// when the cap leaves fewer than the minimum bits per row (a saturated filter
+// passes everything and only costs its load).
+static void join_filter_plan(int64_t n, uint64_t code_max, int packed,
+                             int* mode, uint64_t* arg, int64_t* bytes) {
+  *mode = DSX_JF_NONE;
+  *arg = 0;
+  *bytes = 0;
+  if (!join_filter_enabled()) return;
+  int64_t cap = DSX_JOIN_FILTER_MAX_BYTES;
+  if (const char* e = getenv("DSX_JOIN_FILTER_MAX_BYTES")) cap = atoll(e);
+  int64_t min_bits = DSX_JF_MIN_BITS_PER_KEY;
+  if (const char* e = getenv("DSX_JOIN_FILTER_MIN_BITS")) min_bits = atoll(e);
+  if (packed && (int64_t)dsx_jf_exact_words(code_max) * 4 <= cap) {
+    *mode = DSX_JF_EXACT;
+    *arg = code_max;
+    *bytes = (int64_t)dsx_jf_exact_words(code_max) * 4;
+    return;
+  }
+  int64_t words = 1;  // 32 bits
+  while (words * 32 < DSX_JF_BITS_PER_KEY * n) words <<= 1;
+  while (words > 1 && words * 4 > cap) words >>= 1;
+  if (words * 4 > cap || words * 32 < min_bits * n) return;
+  *mode = DSX_JF_HASHED;
+  *arg = (uint64_t)(words - 1);
+  *bytes = words * 4;
+}
+
+static int hash_build_impl(DsxCtx* c, const uint64_t* codes,
+                           const uint8_t* validity, int64_t n,
+                           uint64_t code_max, bool want_filter,
+                           DsxHashTable** out) {
   if (n > 0xFFFFFFFEll) FAIL(-3, "build side too large for u32 row ids");
   static const double slots_mult = [] {
     const char* e = getenv("DSX_JOIN_SLOTS_MULT");
@@ -1491,26 +1550,66 @@ extern "C" int dsx_hash_build(DsxCtx* c, const uint64_t* codes,
   // codes bounded below 2^32-1 → pack (code,rowid) into the claim word:
   // one random 8-B read per probe instead of two, half the table bytes
   t->packed = (code_max != 0 && code_max < 0xFFFFFFFEull) ? 1 : 0;
+  if (want_filter) {
+    join_filter_plan(n, code_max, t->packed, &t->filter_mode, &t->filter_arg,
+                     &t->filter_bytes);
+    c->join_filter_builds[t->filter_mode]++;
+  }
   if (pool_alloc(c, slots * 8, (void**)&t->keys) ||
       (!t->packed && pool_alloc(c, slots * 4, (void**)&t->vals)) ||
       pool_alloc(c, slots * 4, (void**)&t->matched) ||
-      pool_alloc(c, 4, (void**)&t->dup)) {
+      pool_alloc(c, 4, (void**)&t->dup) ||
+      (t->filter_mode != DSX_JF_NONE &&
+       pool_alloc(c, t->filter_bytes, (void**)&t->filter))) {
     dsx_hash_table_free(t);
     FAIL(-2, "hash table alloc failed (%lld slots)", (long long)slots);
   }
   HIP_TRY(hipMemsetAsync(t->keys, 0xFF, slots * 8, c->stream));
   HIP_TRY(hipMemsetAsync(t->matched, 0, slots * 4, c->stream));
   HIP_TRY(hipMemsetAsync(t->dup, 0, 4, c->stream));
+  if (t->filter)
+    HIP_TRY(hipMemsetAsync(t->filter, 0, t->filter_bytes, c->stream));
   int grid = (int)min((int64_t)MAX_GRID, (n + BLOCK - 1) / BLOCK);
   if (grid > 0) {
     ProfScope ps(c, "k_hash_build");
     hipLaunchKernelGGL(k_hash_build, dim3(grid), dim3(BLOCK), 0, c->stream,
                        codes, validity, n, t->keys, t->vals, slots - 1,
-                       t->packed, t->dup);
+                       t->packed, t->dup, t->filter, t->filter_mode,
+                       t->filter_arg);
   }
   HIP_TRY(hipGetLastError());
   *out = t;
   return 0;
+}
+
+extern "C" int dsx_hash_build(DsxCtx* c, const uint64_t* codes,
+                              const uint8_t* validity, int64_t n,
+                              uint64_t code_max, DsxHashTable** out) {
+  return hash_build_impl(c, codes, validity, n, code_max, false, out);
+}
+
+// dsx_hash_build plus, with key_filter != 0, the key-membership filter that
+// dsx_filter_probe_cols consults (no other probe reads it)
+extern "C" int dsx_hash_build_filtered(DsxCtx* c, const uint64_t* codes,
+                                       const uint8_t* validity, int64_t n,
+                                       uint64_t code_max, int key_filter,
+                                       DsxHashTable** out) {
+  return hash_build_impl(c, codes, validity, n, code_max, key_filter != 0,
+                         out);
+}
+
+// tables built through dsx_hash_build_filtered with key_filter != 0 on this
+// context so far that got a filter of `mode` (0: asked for, none built)
+extern "C" int64_t dsx_join_filter_builds(DsxCtx* c, int mode) {
+  return mode >= 0 && mode < 3 ? c->join_filter_builds[mode] : 0;
+}
+
+extern "C" int dsx_hash_table_filter_mode(const DsxHashTable* t) {
+  return t ? t->filter_mode : DSX_JF_NONE;
+}
+
+extern "C" int64_t dsx_hash_table_filter_bytes(const DsxHashTable* t) {
+  return t ? t->filter_bytes : 0;
 }
 
 extern "C" void dsx_hash_table_free(DsxHashTable* t) {
@@ -1520,6 +1619,7 @@ extern "C" void dsx_hash_table_free(DsxHashTable* t) {
     pool_release(t->ctx, t->vals);
     pool_release(t->ctx, t->matched);
     pool_release(t->ctx, t->dup);
+    pool_release(t->ctx, t->filter);
   }
   delete t;
 }
@@ -2026,7 +2126,9 @@ __global__ void k_fprobe_mask(ProgArg prog, KeyArg K, ColsArg C, int64_t n,
                               const uint64_t* tkeys, const uint32_t* tvals,
                               int64_t tmask, int packed,
                               const unsigned int* dup, uint64_t* mask,
-                              int64_t* block_counts, int64_t* extra) {
+                              int64_t* block_counts, int64_t* extra,
+                              const uint32_t* jf, int jf_mode,
+                              uint64_t jf_arg) {
   int64_t lo, hi;
   block_range(n, 64, lo, hi);
   __shared__ int64_t s_count;
@@ -2045,8 +2147,21 @@ __global__ void k_fprobe_mask(ProgArg prog, KeyArg K, ColsArg C, int64_t n,
       Slot v;
       bool valid = vm_eval<LITE>(prog.ins, prog.len, C, r, v);
       if (valid && v.i != 0 && fp_key_valid(K, C, r)) {  // NULL → False
-        uint32_t bid;
-        hit = fp_probe(tkeys, tvals, tmask, packed, pack_key(K, C, r), bid);
+        // the code of a row with a NULL key is garbage and never gets here
+        uint64_t cde = pack_key(K, C, r);
+        if (jf_mode == DSX_JF_EXACT) {  // bit set <=> build key: no table
+          hit = cde <= jf_arg &&
+                (jf[dsx_jf_exact_word(cde)] & dsx_jf_exact_bit(cde)) != 0;
+        } else {
+          bool pass = true;
+          if (jf_mode == DSX_JF_HASHED) {
+            uint64_t h = dsx_jf_mix64(cde);
+            uint32_t bits = dsx_jf_hashed_bits(h);
+            pass = (jf[dsx_jf_hashed_word(h, jf_arg)] & bits) == bits;
+          }
+          uint32_t bid;
+          if (pass) hit = fp_probe(tkeys, tvals, tmask, packed, cde, bid);
+        }
       }
     }
     uint64_t m = __ballot(hit);
@@ -2146,12 +2261,13 @@ __global__ void k_fprobe_emit(KeyArg K, ColsArg C, int64_t n,
 // the per-shape generated form of k_fprobe_mask (jit_kernels.inc)
 static hipFunction_t fprobe_mask_jit_fn(DsxCtx* c, const ProgArg& P,
                                         const KeyArg& K, const ColsArg& C,
-                                        int packed);
+                                        int packed, int jf_mode);
 static void fprobe_mask_jit_launch(DsxCtx* c, hipFunction_t f, int grid,
                                    const ColsArg& C, int64_t n,
                                    const uint64_t* tkeys, int64_t tmask,
                                    const unsigned int* dup, uint64_t* mask,
-                                   int64_t* block_counts, int64_t* extra);
+                                   int64_t* block_counts, int64_t* extra,
+                                   const uint32_t* jf, uint64_t jf_arg);
 
 extern "C" int64_t dsx_fprobe_jit_launches(DsxCtx* c) {
   return c->fprobe_jit_launches;
@@ -2199,17 +2315,22 @@ extern "C" int dsx_filter_probe_cols(
     {
       // generated kernel first; the interpreter is the fallback (JIT off,
       // DSX_DISABLE_JIT_FPROBE=1, predicate rejected, hipRTC failure)
-      hipFunction_t fj = fprobe_mask_jit_fn(c, P, K, C, t->packed);
+      // DSX_DISABLE_JOINFILTER=1 (read per call) also ignores a filter the
+      // table already has
+      int jf_mode = join_filter_enabled() ? t->filter_mode : DSX_JF_NONE;
+      hipFunction_t fj = fprobe_mask_jit_fn(c, P, K, C, t->packed, jf_mode);
       ProfScope ps(c, "k_fprobe_mask");
       if (fj) {
         fprobe_mask_jit_launch(c, fj, grid, C, n, t->keys, t->slots - 1,
-                               t->dup, mask, block_counts, d_total + 1);
+                               t->dup, mask, block_counts, d_total + 1,
+                               t->filter, t->filter_arg);
       } else {
         auto kern = vm_prog_is_lite(prog, prog_len) ? k_fprobe_mask<true>
                                                     : k_fprobe_mask<false>;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, c->stream, P, K,
                            C, n, t->keys, t->vals, t->slots - 1, t->packed,
-                           t->dup, mask, block_counts, d_total + 1);
+                           t->dup, mask, block_counts, d_total + 1, t->filter,
+                           jf_mode, t->filter_arg);
       }
     }
     hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream,
@@ -3821,14 +3942,19 @@ extern "C" int dsx_jit_pack_source(const DsxKeySpec* keys, int nkeys,
 // words <= 0 selects the shipped value. Host-only: no HIP calls.
 // Returns 0; -1 when the generator rejects the predicate (the caller's
 // interpreter fallback), -2 when buf is too small, -3 on a malformed spec.
-extern "C" int dsx_jit_fprobe_source(const DsxInstr* prog, int prog_len,
-                                     const DsxKeySpec* keys, int nkeys,
-                                     const int32_t* dtypes,
-                                     const uint8_t* has_validity, int ncols,
-                                     int packed, int words, char* buf,
-                                     int64_t cap) {
+// dsx_jit_fprobe_source_mode is the same for a table with a key-membership
+// filter of mode jf_mode (join_filter.h); mode 0 is dsx_jit_fprobe_source.
+// The filter's pointer, size and cap never enter the text.
+extern "C" int dsx_jit_fprobe_source_mode(const DsxInstr* prog, int prog_len,
+                                          const DsxKeySpec* keys, int nkeys,
+                                          const int32_t* dtypes,
+                                          const uint8_t* has_validity,
+                                          int ncols, int packed, int words,
+                                          int jf_mode, char* buf,
+                                          int64_t cap) {
   if (prog_len < 0 || prog_len > DSX_MAX_PROG || nkeys <= 0 ||
-      nkeys > DSX_MAX_KEYS || ncols < 0 || ncols > DSX_MAX_COLS || words > 8)
+      nkeys > DSX_MAX_KEYS || ncols < 0 || ncols > DSX_MAX_COLS || words > 8 ||
+      jf_mode < DSX_JF_NONE || jf_mode > DSX_JF_HASHED)
     return -3;
   ProgArg P{};
   memcpy(P.ins, prog, prog_len * sizeof(DsxInstr));
@@ -3846,11 +3972,22 @@ extern "C" int dsx_jit_fprobe_source(const DsxInstr* prog, int prog_len,
   }
   std::string src =
       jit_fprobe_source(C, K, P, packed != 0,
-                        words <= 0 ? DSX_FPROBE_JIT_WORDS : words);
+                        words <= 0 ? DSX_FPROBE_JIT_WORDS : words, jf_mode);
   if (src.empty()) return -1;
   if ((int64_t)src.size() + 1 > cap) return -2;
   memcpy(buf, src.c_str(), src.size() + 1);
   return 0;
+}
+
+extern "C" int dsx_jit_fprobe_source(const DsxInstr* prog, int prog_len,
+                                     const DsxKeySpec* keys, int nkeys,
+                                     const int32_t* dtypes,
+                                     const uint8_t* has_validity, int ncols,
+                                     int packed, int words, char* buf,
+                                     int64_t cap) {
+  return dsx_jit_fprobe_source_mode(prog, prog_len, keys, nkeys, dtypes,
+                                    has_validity, ncols, packed, words,
+                                    DSX_JF_NONE, buf, cap);
 }
 
 // dsx_jit_compile_check — TEST INFRASTRUCTURE: hipRTC-compile a generated

@@ -713,11 +713,36 @@ static JitEntry* jit_source_entry(DsxCtx* c, const std::string& src) {
 // ---------------------------------------------------------------------------
 #define DSX_FPROBE_JIT_WORDS 1  // shipped R
 
+// join_filter.h once more, as text for the generated source (the header
+// explains the DSX_JF_CODE form)
+#undef DSX_JF_CODE
+#define DSX_JF_CODE(...) #__VA_ARGS__
+static const char* JIT_JOIN_FILTER =
+#include "join_filter.h"
+    ;
+#undef DSX_JF_CODE
+#define DSX_JF_CODE(...) __VA_ARGS__
+
+// jf_mode (join_filter.h) is part of the text, so each mode compiles once per
+// shape; the filter pointer and its code_max / word mask are arguments.
+//   exact:  phase C loads one filter word per row instead of a slot, and
+//           hit = alive & bit. No slot load, no chain, tkeys untouched.
+//   hashed: the filter word is loaded first; only lanes that pass it load
+//           their first slot and walk the chain.
+// Both keep the branch-free load shape: a dead lane (failed predicate, NULL
+// key, tail row) reads filter word 0 as it reads slot 0 without a filter, and
+// so does a live lane whose code is past code_max (a miss). The code of a row
+// under a NULL key is garbage and never indexes the filter.
 static std::string jit_fprobe_source(const ColsArg& C, const KeyArg& K,
-                                     const ProgArg& P, bool packed, int R) {
+                                     const ProgArg& P, bool packed, int R,
+                                     int jf_mode = DSX_JF_NONE) {
   if (R < 1 || R > 8 || K.nkeys < 1) return "";
+  if (jf_mode < DSX_JF_NONE || jf_mode > DSX_JF_HASHED) return "";
   std::ostringstream os;
   os << JIT_PRELUDE;
+  if (jf_mode != DSX_JF_NONE)
+    os << "#define DSX_JF_HD __device__ __forceinline__\n"
+       << JIT_JOIN_FILTER << "\n";
   char k;
   if (!jit_emit_fn(os, "eval_pred", P.ins, P.len, &C, &k)) return "";
   jit_emit_pack(os, K, &C);
@@ -731,6 +756,98 @@ static std::string jit_fprobe_source(const ColsArg& C, const KeyArg& K,
   const char* match = packed ? "(k[j] >> 32) == code[j]" : "k[j] == code[j]";
   os << "#define R " << R << "\n#define EMPTY_KEY 0xFFFFFFFFFFFFFFFFull\n"
      << "#define MATCH(j) (" << match << ")\n";
+  if (jf_mode != DSX_JF_NONE) {
+    os << R"(
+extern "C" __global__ void __launch_bounds__(BLOCK) j_fprobe_mask(
+    ColsArg C, i64 n, const u64* __restrict__ tkeys, i64 tmask,
+    const u32* __restrict__ dup, u64* __restrict__ mask,
+    i64* __restrict__ block_counts, i64* __restrict__ extra,
+    const u32* __restrict__ jf, u64 jf_arg) {
+  i64 lo, hi; block_range(n, 64, lo, hi);
+  __shared__ u64 s_count;
+  if (threadIdx.x == 0) {
+    s_count = 0;
+    if (blockIdx.x == 0) extra[0] = (i64)*dup;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const i64 w0 = (lo + 63) / 64, w1 = (hi + 63) / 64;  // lo == hi: no words
+  i64 local = 0;
+  for (i64 wb = w0 + (i64)wid * R; wb < w1; wb += (BLOCK / 64) * R) {
+    bool alive[R]; u64 code[R]; u64 fw[R]; u32 f[R]; bool hit[R];
+    // A: all column loads of the R words, in one branch-free block
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      i64 r = (wb + j) * 64 + lane;
+      i64 rc = r < n ? r : n - 1;  // clamped: the loads stay unconditional
+      i64 pv; bool ok = eval_pred(C, rc, pv);
+      bool kv = jit_key_valid(C, rc);
+      code[j] = jit_pack(C, rc);
+      alive[j] = (r < hi) & ok & (pv != 0) & kv;  // NULL predicate: false
+    }
+)";
+    if (jf_mode == DSX_JF_EXACT)
+      os << R"(    // B: filter words; jf_arg = code_max
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      alive[j] = alive[j] & (code[j] <= jf_arg);
+      fw[j] = alive[j] ? dsx_jf_exact_word(code[j]) : 0;
+    }
+    // C: one filter word per row, back to back; bit set <=> build key
+#pragma unroll
+    for (int j = 0; j < R; j++) f[j] = jf[fw[j]];
+#pragma unroll
+    for (int j = 0; j < R; j++)
+      hit[j] = alive[j] & ((f[j] & dsx_jf_exact_bit(code[j])) != 0);
+)";
+    else
+      os << R"(    // B: hashes and filter words; jf_arg = filter words - 1
+    u64 h[R]; i64 s[R]; u64 k[R];
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      h[j] = alive[j] ? dsx_jf_mix64(code[j]) : 0;
+      fw[j] = alive[j] ? dsx_jf_hashed_word(h[j], jf_arg) : 0;
+    }
+    // C: filter words, then the first slots of the lanes that passed
+#pragma unroll
+    for (int j = 0; j < R; j++) f[j] = jf[fw[j]];
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      u32 bits = dsx_jf_hashed_bits(h[j]);
+      alive[j] = alive[j] & ((f[j] & bits) == bits);
+      s[j] = alive[j] ? (i64)(h[j] & (u64)tmask) : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < R; j++) k[j] = tkeys[s[j]];
+    // D: the rest of each chain, one word after another
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      hit[j] = false;
+      bool go = alive[j];
+      while (go) {
+        if (k[j] == EMPTY_KEY) break;
+        if (MATCH(j)) { hit[j] = true; break; }
+        s[j] = (s[j] + 1) & tmask;
+        k[j] = tkeys[s[j]];
+      }
+    }
+)";
+    os << R"(#pragma unroll
+    for (int j = 0; j < R; j++) {
+      u64 m = __builtin_amdgcn_ballot_w64(hit[j]);
+      if (lane == 0 && wb + j < w1) {
+        mask[wb + j] = m;
+        local += __builtin_popcountll(m);
+      }
+    }
+  }
+  if (lane == 0) atomicAdd(&s_count, (u64)local);
+  __syncthreads();
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = (i64)s_count;
+}
+)";
+    return os.str();
+  }
   os << R"(
 extern "C" __global__ void __launch_bounds__(BLOCK) j_fprobe_mask(
     ColsArg C, i64 n, const u64* __restrict__ tkeys, i64 tmask,
@@ -815,10 +932,11 @@ static int jit_fprobe_words() {
 // generator rejects the predicate, or hipRTC failed (negative-cached)
 static hipFunction_t fprobe_mask_jit_fn(DsxCtx* c, const ProgArg& P,
                                         const KeyArg& K, const ColsArg& C,
-                                        int packed) {
+                                        int packed, int jf_mode) {
   if (!jit_enabled() || !jit_fprobe_enabled()) return nullptr;
   JitEntry* je = jit_source_entry(
-      c, jit_fprobe_source(C, K, P, packed != 0, jit_fprobe_words()));
+      c, jit_fprobe_source(C, K, P, packed != 0, jit_fprobe_words(),
+                           jf_mode));
   return je ? jit_fn(c, je, "j_fprobe_mask") : nullptr;
 }
 
@@ -826,9 +944,13 @@ static void fprobe_mask_jit_launch(DsxCtx* c, hipFunction_t f, int grid,
                                    const ColsArg& C, int64_t n,
                                    const uint64_t* tkeys, int64_t tmask,
                                    const unsigned int* dup, uint64_t* mask,
-                                   int64_t* block_counts, int64_t* extra) {
+                                   int64_t* block_counts, int64_t* extra,
+                                   const uint32_t* jf, uint64_t jf_arg) {
   ColsArg Ca = C;
-  void* args[] = {&Ca, &n, &tkeys, &tmask, &dup, &mask, &block_counts, &extra};
+  // jf and jf_arg are parameters of the filtered modes' kernels only; the
+  // launch reads as many entries as the kernel declares
+  void* args[] = {&Ca,   &n,           &tkeys, &tmask, &dup,
+                  &mask, &block_counts, &extra, &jf,    &jf_arg};
   hipModuleLaunchKernel(f, grid, 1, 1, BLOCK, 1, 1, 0, c->stream, args,
                         nullptr);
   c->fprobe_jit_launches++;

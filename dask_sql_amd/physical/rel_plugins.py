@@ -1209,7 +1209,9 @@ class DaskJoinPlugin(BaseRelPlugin):
                     cc_rhs.get_backend_by_frontend_name(frontend))
             on_probe = (side == "l") == probe_is_l
             (p_items if on_probe else b_items).append((i, col))
-        table = runtime.hash_build(bcodes, bval, code_max=space - 1)
+        # only the fused filter-probe reads the key-membership filter
+        table = runtime.hash_build(bcodes, bval, code_max=space - 1,
+                                   key_filter=pending is not None)
         try:
             res = None
             if pending is not None:

@@ -488,17 +488,46 @@ class Runtime:
         )
         return out, space
 
-    def hash_build(self, codes: DeviceColumn, validity_ptr=None, code_max=0):
+    def hash_build(self, codes: DeviceColumn, validity_ptr=None, code_max=0,
+                   key_filter=False):
+        """key_filter: also build the key-membership filter that
+        filter_probe_cols consults (dsx_hash_build_filtered); only a table
+        that goes to filter_probe_cols asks for it."""
         t = ct.c_void_p()
+        vptr = ct.c_void_p(validity_ptr) if validity_ptr else None
+        if key_filter:
+            _check(
+                self.lib,
+                self.lib.dsx_hash_build_filtered(
+                    self.ctx, ct.c_void_p(codes.data), vptr,
+                    ct.c_int64(codes.len), ct.c_uint64(code_max), ct.c_int(1),
+                    ct.byref(t)),
+                "dsx_hash_build_filtered",
+            )
+            return t
         _check(
             self.lib,
-            self.lib.dsx_hash_build(self.ctx, ct.c_void_p(codes.data),
-                                    ct.c_void_p(validity_ptr) if validity_ptr else None,
+            self.lib.dsx_hash_build(self.ctx, ct.c_void_p(codes.data), vptr,
                                     ct.c_int64(codes.len),
                                     ct.c_uint64(code_max), ct.byref(t)),
             "dsx_hash_build",
         )
         return t
+
+    def hash_table_filter(self, table):
+        """(mode, bytes) of the table's key-membership filter: mode 0 none,
+        1 exact bitmap, 2 hashed (csrc/join_filter.h)."""
+        self.lib.dsx_hash_table_filter_mode.restype = ct.c_int
+        self.lib.dsx_hash_table_filter_bytes.restype = ct.c_int64
+        return (int(self.lib.dsx_hash_table_filter_mode(table)),
+                int(self.lib.dsx_hash_table_filter_bytes(table)))
+
+    def join_filter_builds(self):
+        """(none, exact, hashed): how many hash_build(key_filter=True) calls
+        on this runtime ended in each filter mode so far."""
+        self.lib.dsx_join_filter_builds.restype = ct.c_int64
+        return tuple(int(self.lib.dsx_join_filter_builds(self.ctx, ct.c_int(m)))
+                     for m in range(3))
 
     def hash_probe(self, table, codes: DeviceColumn, join_type,
                    validity_ptr=None, mark_matched=False):

@@ -216,6 +216,21 @@ typedef struct DsxHashTable DsxHashTable;
  * (code,rowid) into one 8-byte slot — one random read per probe. */
 int dsx_hash_build(DsxCtx* ctx, const uint64_t* codes, const uint8_t* validity,
                    int64_t n, uint64_t code_max, DsxHashTable** out);
+/* dsx_hash_build plus, with key_filter != 0, a key-membership filter over the
+ * build keys that dsx_filter_probe_cols consults before (or instead of) the
+ * table: mode 1 is an exact bitmap over codes 0..code_max (packed tables whose
+ * bitmap fits the byte cap), mode 2 a blocked two-bit Bloom filter, mode 0 no
+ * filter. The cap is DSX_JOIN_FILTER_MAX_BYTES (csrc/join_filter.h; the env
+ * variable of the same name overrides it per call); DSX_DISABLE_JOINFILTER=1,
+ * read per call, builds and reads no filter. */
+int dsx_hash_build_filtered(DsxCtx* ctx, const uint64_t* codes,
+                            const uint8_t* validity, int64_t n,
+                            uint64_t code_max, int key_filter,
+                            DsxHashTable** out);
+int dsx_hash_table_filter_mode(const DsxHashTable* t);
+int64_t dsx_hash_table_filter_bytes(const DsxHashTable* t);
+/* filtered builds (key_filter != 0) on ctx so far that ended in `mode` */
+int64_t dsx_join_filter_builds(DsxCtx* ctx, int mode);
 void dsx_hash_table_free(DsxHashTable* t);
 
 enum DsxJoinType {  /* reference join.py:41-48 JOIN_TYPE_MAPPING */
@@ -473,6 +488,12 @@ int dsx_jit_pack_source(const DsxKeySpec* keys, int nkeys,
  * words per wave iteration (1..8, <= 0 for the shipped value). Returns 0;
  * -1 when the generator rejects the predicate (callers fall back to the
  * interpreter kernel), -2 when buf is too small, -3 on a malformed spec. */
+int dsx_jit_fprobe_source_mode(const DsxInstr* prog, int prog_len,
+                               const DsxKeySpec* keys, int nkeys,
+                               const int32_t* dtypes,
+                               const uint8_t* has_validity, int ncols,
+                               int packed, int words, int jf_mode, char* buf,
+                               int64_t cap);  /* jf_mode 0: the entry below */
 int dsx_jit_fprobe_source(const DsxInstr* prog, int prog_len,
                           const DsxKeySpec* keys, int nkeys,
                           const int32_t* dtypes, const uint8_t* has_validity,
