@@ -16,6 +16,7 @@
 
 #include "../../include/dsxhip.h"
 #include "join_filter.h"
+#include "gb_finish.h"
 
 #define BLOCK 256
 #define WAVES_PER_BLOCK (BLOCK / 64)
@@ -3020,6 +3021,163 @@ __global__ void k_groupby_emit(const uint64_t* tkeys, int64_t slots,
   }
 }
 
+// ---- finish: every group-by output column in one launch --------------------
+// (dsx_hash_groupby_cols; arithmetic in gb_finish.h). The argument block is
+// passed BY VALUE: through a global pointer the compiler reloads every
+// destination pointer per store (note at k_hash_probe_mat); as a kernel
+// argument its launch-uniform fields sit in SGPRs, and the loops below are
+// fully unrolled so each field is read at a compile-time index.
+struct GbFinishArg {
+  DsxGbKeyPlan key[DSX_MAX_KEYS];
+  uint64_t* kdata[DSX_MAX_KEYS];
+  uint8_t* kvalid[DSX_MAX_KEYS];  // nullptr: the key cannot be NULL
+  uint64_t* adata[DSX_MAX_AGGS];
+  uint8_t* avalid[DSX_MAX_AGGS];  // nullptr for COUNT
+  int32_t kind[DSX_MAX_AGGS];     // DSX_GBF_*
+  int32_t vidx[DSX_MAX_AGGS];     // accumulator index in the source layout
+  int32_t nn[DSX_MAX_AGGS];       // never-NULL input: count = group rows
+  int32_t nkeys, ncalls;
+};
+
+template <class Src>
+__device__ __forceinline__ void gb_finish_row(const GbFinishArg& F, int64_t o,
+                                              uint64_t code, const Src& src) {
+#pragma unroll
+  for (int j = 0; j < DSX_MAX_KEYS; j++) {
+    if (j >= F.nkeys) break;
+    uint64_t bits;
+    int valid = dsx_gbf_key_value(code, F.key[j], &bits);
+    F.kdata[j][o] = bits;
+    if (F.kvalid[j]) F.kvalid[j][o] = (uint8_t)valid;
+  }
+#pragma unroll
+  for (int a = 0; a < DSX_MAX_AGGS; a++) {
+    if (a >= F.ncalls) break;
+    uint64_t cnt = src.count(F.vidx[a], F.nn[a]);
+    uint64_t raw = F.kind[a] == DSX_GBF_COUNT ? 0ull : src.raw(F.vidx[a]);
+    uint64_t bits;
+    int valid = dsx_gbf_finalize(F.kind[a], raw, cnt, &bits);
+    F.adata[a][o] = bits;
+    if (F.avalid[a]) F.avalid[a][o] = (uint8_t)valid;
+  }
+}
+
+// partition path: reads the aggregate's AoS temporaries as they are (all
+// inputs never-NULL there, so every count is the group's row count)
+struct GbSrcAos {
+  const uint64_t* vals;  // this group's [nvals] record
+  uint64_t gcnt;
+  __device__ __forceinline__ uint64_t raw(int v) const { return vals[v]; }
+  __device__ __forceinline__ uint64_t count(int, int) const { return gcnt; }
+};
+
+__global__ void __launch_bounds__(BLOCK)
+k_gb_finish_aos(GbFinishArg F, const uint64_t* tmp_codes,
+                const uint64_t* tmp_vals, const unsigned long long* tmp_gcnt,
+                int64_t G, int nvals) {
+  int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * BLOCK;
+  for (; i < G; i += stride) {
+    GbSrcAos src{tmp_vals + i * nvals, (uint64_t)tmp_gcnt[i]};
+    gb_finish_row(F, i, tmp_codes[i], src);
+  }
+}
+
+// direct / global paths: the compaction of k_groupby_emit with the column
+// writes fused in — reads the accumulator tables, no [naggs][G] slabs
+struct GbSrcTable {
+  const uint64_t* g_vals;
+  const unsigned long long* g_cnts;
+  uint64_t gcnt;
+  int64_t slots, s;
+  __device__ __forceinline__ uint64_t raw(int a) const {
+    return g_vals[(int64_t)a * slots + s];
+  }
+  __device__ __forceinline__ uint64_t count(int a, int nn) const {
+    return nn ? gcnt : (uint64_t)g_cnts[(int64_t)a * slots + s];
+  }
+};
+
+template <int DIRECT>
+__global__ void __launch_bounds__(BLOCK)
+k_gb_finish_table(GbFinishArg F, const uint64_t* tkeys, int64_t slots,
+                  const uint64_t* g_vals, const unsigned long long* g_cnts,
+                  const unsigned long long* g_gcnt, int64_t G,
+                  unsigned long long* counter) {
+  int64_t lo, hi;
+  block_range(slots, 1, lo, hi);
+  for (int64_t s = lo + threadIdx.x; s < hi; s += BLOCK) {
+    bool live = DIRECT ? (g_gcnt[s] > 0) : (tkeys[s] != EMPTY_KEY);
+    if (!live) continue;
+    int64_t o = (int64_t)atomicAdd(counter, 1ull);
+    if (o >= G) continue;  // cannot happen: G counted with the same test
+    GbSrcTable src{g_vals, g_cnts, (uint64_t)g_gcnt[s], slots, s};
+    gb_finish_row(F, o, DIRECT ? (uint64_t)s : tkeys[s], src);
+  }
+}
+
+// what dsx_hash_groupby_cols asks of the group-by drivers below
+struct GbFinishReq {
+  const DsxGbFinishCall* calls;
+  int ncalls;
+  void** out_datas;      // [nkeys + ncalls], keys first
+  uint8_t** out_valids;
+};
+
+// allocate the output columns for G groups and fill F. On failure nothing
+// stays allocated.
+static int gb_finish_alloc(DsxCtx* c, const GbFinishReq& R, const KeyArg& K,
+                           const AggArg& A, int64_t G, GbFinishArg* F) {
+  memset(F, 0, sizeof(*F));
+  F->nkeys = K.nkeys;
+  F->ncalls = R.ncalls;
+  int nout = K.nkeys + R.ncalls;
+  for (int i = 0; i < nout; i++) {
+    R.out_datas[i] = nullptr;
+    R.out_valids[i] = nullptr;
+  }
+  int64_t g1 = G > 0 ? G : 1;
+  int rc = 0;
+  for (int i = 0; i < nout && !rc; i++) {
+    bool want_valid;
+    if (i < K.nkeys) {
+      const DsxKeySpec& k = K.k[i];
+      uint64_t space = k.mode == 1
+                           ? 1
+                           : (uint64_t)k.range + (k.nullable ? 1 : 0);
+      F->key[i] = dsx_gbf_key_plan(K.stride[i], space, k.min, k.nullable,
+                                   k.mode);
+      want_valid = k.mode == 1 || k.nullable;
+    } else {
+      const DsxGbFinishCall& cl = R.calls[i - K.nkeys];
+      F->kind[i - K.nkeys] = cl.kind;
+      F->vidx[i - K.nkeys] = cl.agg;
+      F->nn[i - K.nkeys] = A.never_null[cl.agg];
+      want_valid = cl.kind != DSX_GBF_COUNT;
+    }
+    rc = pool_alloc(c, g1 * 8, &R.out_datas[i]);
+    if (!rc && want_valid) rc = pool_alloc(c, g1, (void**)&R.out_valids[i]);
+  }
+  if (rc) {
+    for (int i = 0; i < nout; i++) {
+      if (R.out_datas[i]) pool_release(c, R.out_datas[i]);
+      if (R.out_valids[i]) pool_release(c, R.out_valids[i]);
+      R.out_datas[i] = nullptr;
+      R.out_valids[i] = nullptr;
+    }
+    return rc;
+  }
+  for (int i = 0; i < K.nkeys; i++) {
+    F->kdata[i] = (uint64_t*)R.out_datas[i];
+    F->kvalid[i] = R.out_valids[i];
+  }
+  for (int i = 0; i < R.ncalls; i++) {
+    F->adata[i] = (uint64_t*)R.out_datas[K.nkeys + i];
+    F->avalid[i] = R.out_valids[K.nkeys + i];
+  }
+  return 0;
+}
+
 __global__ void k_count_live(const uint64_t* tkeys,
                              const unsigned long long* g_gcnt, int64_t slots,
                              int direct, unsigned long long* counter) {
@@ -3085,7 +3243,8 @@ static int groupby_partition_impl(
     const DsxAggSpec* aggs_arr, std::vector<DsxInstr>& progs,
     std::vector<int32_t>& lens, int naggs, int64_t g_est, uint64_t key_space,
     uint64_t** out_codes, void** out_vals, uint64_t** out_counts,
-    int64_t* out_groups, bool* fell_back, int direct_shift, bool* redo) {
+    int64_t* out_groups, bool* fell_back, int direct_shift, bool* redo,
+    const GbFinishReq* fin) {
   *fell_back = false;
   // SoA u32-code records (u32 codes + u64 vals) — MEASURED REGRESSION at C2
   // (35.0 vs 45.8 G rows/s): splitting the record doubles the number of
@@ -3135,7 +3294,21 @@ static int groupby_partition_impl(
     const char* e = getenv("DSX_GB_GRID");
     return e ? atoi(e) : MAX_GRID;
   }();
-  int grid = (int)min((int64_t)max_grid, (n + BLOCK - 1) / BLOCK);
+  // Rows-per-block bound: the per-block histogram is
+  // grid × nb counters, which the scan reads and writes and the scatter
+  // reads again — at Q3 (3 M rows, nb 4096) 2048 blocks make it larger than
+  // the input. So a block owns at least nb rows: the largest power of two g
+  // with g·nb ≤ n, floored at one block per CU (256; hist and scatter lose
+  // more below it than the scan gains) and capped as before. C2 (100 M rows,
+  // nb 248) keeps 2048. DSX_GB_GRID stays an upper cap.
+  int64_t g_rows = 256;
+  while (g_rows < MAX_GRID && g_rows * 2 * nb <= n) g_rows <<= 1;
+  int grid = (int)min(min((int64_t)max_grid, (n + BLOCK - 1) / BLOCK), g_rows);
+  if (grid == 0 && fin) {
+    GbFinishArg F;
+    *out_groups = 0;
+    return gb_finish_alloc(c, *fin, K, A, 0, &F);
+  }
   if (grid == 0) {  // empty input → empty output
     int rc2 = pool_alloc(c, 8, (void**)out_codes);
     if (!rc2) rc2 = pool_alloc(c, 8, out_vals);
@@ -3296,10 +3469,13 @@ static int groupby_partition_impl(
         hipModuleLaunchKernel(f_hist, grid, 1, 1, BLOCK, 1, 1,
                               (unsigned)(nb * 4), c->stream, args, nullptr);
       }
-      hipLaunchKernelGGL(k_gbpart_scan, dim3(nb / 8), dim3(BLOCK), 0,
-                         c->stream, d_hist, grid, nb, d_totals);
-      hipLaunchKernelGGL(k_gbpart_bases, dim3(1), dim3(1024), 0, c->stream,
-                         d_totals, nb, d_bases);
+      {
+        ProfScope ps(c, "k_gbpart_scan");
+        hipLaunchKernelGGL(k_gbpart_scan, dim3(nb / 8), dim3(BLOCK), 0,
+                           c->stream, d_hist, grid, nb, d_totals);
+        hipLaunchKernelGGL(k_gbpart_bases, dim3(1), dim3(1024), 0, c->stream,
+                           d_totals, nb, d_bases);
+      }
       if (c->gb_hist_cache_on) {
         if (c->gb_hist_cache.size() >= 6) {
           pool_release(c, c->gb_hist_cache.front().hist);
@@ -3396,10 +3572,13 @@ static int groupby_partition_impl(
       hipLaunchKernelGGL(k_gbpart_hist, dim3(grid), dim3(BLOCK),
                          (size_t)nb * 4, c->stream, C, n, d_K, P, nb, d_hist);
     }
-    hipLaunchKernelGGL(k_gbpart_scan, dim3(nb / 8), dim3(BLOCK), 0, c->stream,
-                       d_hist, grid, nb, d_totals);
-    hipLaunchKernelGGL(k_gbpart_bases, dim3(1), dim3(1024), 0, c->stream,
-                       d_totals, nb, d_bases);
+    {
+      ProfScope ps(c, "k_gbpart_scan");
+      hipLaunchKernelGGL(k_gbpart_scan, dim3(nb / 8), dim3(BLOCK), 0,
+                         c->stream, d_hist, grid, nb, d_totals);
+      hipLaunchKernelGGL(k_gbpart_bases, dim3(1), dim3(1024), 0, c->stream,
+                         d_totals, nb, d_bases);
+    }
     {
       ProfScope ps(c, "k_gbpart_scatter");
       hipLaunchKernelGGL(k_gbpart_scatter, dim3(grid), dim3(BLOCK),
@@ -3458,6 +3637,26 @@ static int groupby_partition_impl(
     *fell_back = true;
     return 0;
   }
+  if (fin) {
+    // one launch reads the AoS temporaries and writes every output column;
+    // no slabs, and no synchronize after it: the scratch arena it reads is
+    // reused only by later work on the same stream
+    GbFinishArg F;
+    int rc2 = gb_finish_alloc(c, *fin, K, A, (int64_t)G, &F);
+    if (rc2) return rc2;
+    for (int i = 0; i < F.ncalls; i++)
+      F.vidx[i] = val_of[F.vidx[i]] < 0 ? 0 : val_of[F.vidx[i]];
+    if (G > 0) {
+      int g2 = (int)min((int64_t)MAX_GRID, ((int64_t)G + BLOCK - 1) / BLOCK);
+      ProfScope ps(c, "k_gbpart_finalize");
+      hipLaunchKernelGGL(k_gb_finish_aos, dim3(g2), dim3(BLOCK), 0, c->stream,
+                         F, d_tmp_codes, d_tmp_vals, d_tmp_gcnt, (int64_t)G,
+                         nvals ? nvals : 1);
+    }
+    HIP_TRY(hipGetLastError());
+    *out_groups = (int64_t)G;
+    return 0;
+  }
   {
     int rc2 = pool_alloc(c, (G > 0 ? G : 1) * 8, (void**)out_codes);
     if (!rc2) rc2 = pool_alloc(c, (G > 0 ? G : 1) * 8 * naggs, out_vals);
@@ -3486,7 +3685,8 @@ static int groupby_partition(DsxCtx* c, ColsArg& C, int64_t n, KeyArg& K,
                              int64_t g_est, uint64_t key_space,
                              uint64_t** out_codes,
                              void** out_vals, uint64_t** out_counts,
-                             int64_t* out_groups, bool* fell_back) {
+                             int64_t* out_groups, bool* fell_back,
+                             const GbFinishReq* fin) {
   int nvals_probe = 0;
   for (int a = 0; a < naggs; a++)
     if (A.op[a] != DSX_AGG_COUNT) nvals_probe++;
@@ -3496,13 +3696,14 @@ static int groupby_partition(DsxCtx* c, ColsArg& C, int64_t n, KeyArg& K,
     int rc = groupby_partition_impl(c, C, n, K, P, A, aggs_arr, progs, lens,
                                     naggs, g_est, key_space, out_codes,
                                     out_vals, out_counts, out_groups,
-                                    fell_back, ds, &redo);
+                                    fell_back, ds, &redo, fin);
     if (rc != 0 || !redo) return rc;
   }
   bool redo = false;
   return groupby_partition_impl(c, C, n, K, P, A, aggs_arr, progs, lens,
                                 naggs, g_est, key_space, out_codes, out_vals,
-                                out_counts, out_groups, fell_back, -1, &redo);
+                                out_counts, out_groups, fell_back, -1, &redo,
+                                fin);
 }
 
 /* Toggle the per-table histogram cache (off for externally-backed key
@@ -3512,12 +3713,13 @@ extern "C" int dsx_gb_hist_cache_enable(DsxCtx* c, int enable) {
   return 0;
 }
 
-extern "C" int dsx_hash_groupby(DsxCtx* c, const DsxColumn* cols, int ncols,
-                                int64_t n, const DsxKeySpec* keys, int nkeys,
-                                const DsxInstr* pred,
-                                int pred_len, const DsxAggSpec* aggs, int naggs,
-                                uint64_t** out_codes, void** out_vals,
-                                uint64_t** out_counts, int64_t* out_groups) {
+static int hash_groupby_impl(DsxCtx* c, const DsxColumn* cols, int ncols,
+                             int64_t n, const DsxKeySpec* keys, int nkeys,
+                             const DsxInstr* pred, int pred_len,
+                             const DsxAggSpec* aggs, int naggs,
+                             uint64_t** out_codes, void** out_vals,
+                             uint64_t** out_counts, int64_t* out_groups,
+                             const GbFinishReq* fin) {
   if (naggs > DSX_MAX_AGGS || ncols > DSX_MAX_COLS || pred_len > DSX_MAX_PROG ||
       nkeys > DSX_MAX_KEYS)
     FAIL(-3, "groupby spec too large");
@@ -3589,7 +3791,7 @@ extern "C" int dsx_hash_groupby(DsxCtx* c, const DsxColumn* cols, int ncols,
       bool fell_back = false;
       int prc = groupby_partition(c, C, n, K, P, A, aggs, progs, lens, naggs,
                                   g_est, key_space, out_codes, out_vals,
-                                  out_counts, out_groups, &fell_back);
+                                  out_counts, out_groups, &fell_back, fin);
       if (prc != 0) return prc;
       if (!fell_back) return 0;
     }
@@ -3713,6 +3915,29 @@ extern "C" int dsx_hash_groupby(DsxCtx* c, const DsxColumn* cols, int ncols,
     HIP_TRY(hipMemcpyAsync(&G, d_counter, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
 
+    if (fin) {
+      // compaction and column writes in one launch, straight from the
+      // accumulator tables; returns with it queued (see the partition path)
+      GbFinishArg F;
+      int rc2 = gb_finish_alloc(c, *fin, K, A, (int64_t)G, &F);
+      if (rc2) return rc2;
+      HIP_TRY(hipMemsetAsync(d_counter, 0, 8, c->stream));
+      if (G > 0) {
+        int g = (int)min((int64_t)MAX_GRID, (slots + BLOCK - 1) / BLOCK);
+        ProfScope ps(c, "k_groupby_finish");
+        if (direct)
+          hipLaunchKernelGGL(k_gb_finish_table<1>, dim3(g), dim3(BLOCK), 0,
+                             c->stream, F, d_tkeys, slots, d_vals, d_cnts,
+                             d_gcnt, (int64_t)G, d_counter);
+        else
+          hipLaunchKernelGGL(k_gb_finish_table<0>, dim3(g), dim3(BLOCK), 0,
+                             c->stream, F, d_tkeys, slots, d_vals, d_cnts,
+                             d_gcnt, (int64_t)G, d_counter);
+      }
+      HIP_TRY(hipGetLastError());
+      *out_groups = (int64_t)G;
+      return 0;
+    }
     {
       int rc2 = pool_alloc(c, (G > 0 ? G : 1) * 8, (void**)out_codes);
       if (!rc2) rc2 = pool_alloc(c, (G > 0 ? G : 1) * 8 * naggs, out_vals);
@@ -3740,6 +3965,52 @@ extern "C" int dsx_hash_groupby(DsxCtx* c, const DsxColumn* cols, int ncols,
     *out_groups = (int64_t)G;
     return 0;
   }
+}
+
+extern "C" int dsx_hash_groupby(DsxCtx* c, const DsxColumn* cols, int ncols,
+                                int64_t n, const DsxKeySpec* keys, int nkeys,
+                                const DsxInstr* pred,
+                                int pred_len, const DsxAggSpec* aggs, int naggs,
+                                uint64_t** out_codes, void** out_vals,
+                                uint64_t** out_counts, int64_t* out_groups) {
+  return hash_groupby_impl(c, cols, ncols, n, keys, nkeys, pred, pred_len,
+                           aggs, naggs, out_codes, out_vals, out_counts,
+                           out_groups, nullptr);
+}
+
+extern "C" int dsx_hash_groupby_cols(
+    DsxCtx* c, const DsxColumn* cols, int ncols, int64_t n,
+    const DsxKeySpec* keys, int nkeys, const DsxInstr* pred, int pred_len,
+    const DsxAggSpec* aggs, int naggs, const DsxGbFinishCall* calls,
+    int ncalls, void** out_datas, uint8_t** out_valids, int64_t* out_groups) {
+  if (nkeys < 1 || nkeys > DSX_MAX_KEYS || naggs > DSX_MAX_AGGS ||
+      ncalls < 0 || ncalls > DSX_MAX_AGGS)
+    FAIL(-3, "groupby finish spec too large or without keys");
+  for (int i = 0; i < ncalls; i++) {
+    int a = calls[i].agg;
+    if (a < 0 || a >= naggs) FAIL(-3, "finish call names no accumulator");
+    int want;
+    switch (calls[i].kind) {
+      case DSX_GBF_COUNT: want = -1; break;  // any accumulator has a count
+      case DSX_GBF_SUM_I: want = DSX_AGG_SUM_I64; break;
+      case DSX_GBF_SUM_F:
+      case DSX_GBF_AVG: want = DSX_AGG_SUM_F64; break;
+      case DSX_GBF_MIN_I: want = DSX_AGG_MIN_I64; break;
+      case DSX_GBF_MAX_I: want = DSX_AGG_MAX_I64; break;
+      case DSX_GBF_MIN_F: want = DSX_AGG_MIN_F64; break;
+      case DSX_GBF_MAX_F: want = DSX_AGG_MAX_F64; break;
+      default: FAIL(-3, "unknown finish kind %d", calls[i].kind);
+    }
+    if (want >= 0 && aggs[a].op != want)
+      FAIL(-3, "finish kind %d does not fit accumulator op %d",
+           calls[i].kind, aggs[a].op);
+  }
+  GbFinishReq R{calls, ncalls, out_datas, out_valids};
+  uint64_t* oc = nullptr;
+  void* ov = nullptr;
+  uint64_t* on = nullptr;
+  return hash_groupby_impl(c, cols, ncols, n, keys, nkeys, pred, pred_len,
+                           aggs, naggs, &oc, &ov, &on, out_groups, &R);
 }
 
 // ---------------------------------------------------------------------------

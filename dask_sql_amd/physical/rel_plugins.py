@@ -1802,6 +1802,33 @@ class DaskAggregatePlugin(BaseRelPlugin):
                                                OP_DIV_F64, OP_I64_TO_F64)
         if slab is None:
             slab = list(range(len(calls)))
+        import os
+        if (group_meta and not key_restore
+                and all(f in runtime.GB_FIN_KINDS for f in fins)
+                and os.environ.get("DSX_DISABLE_GBFINISH") != "1"):
+            # keys unpacked and calls finalized by the group-by itself, one
+            # launch for all output columns (dsx_hash_groupby_cols). Densified
+            # float keys (host LUT) and the stddev family keep the code below.
+            kcols, acols, G = runtime.hash_groupby_cols(
+                cols, n_rows, keyspecs, pred_prog, specs,
+                list(zip(fins, slab)))
+            out_cols = {}
+            order_names = []
+            for ks, (name, src), col in zip(keyspecs, group_meta, kcols):
+                if not (len(ks) > 4 and ks[4] == 1) and \
+                        getattr(src, "dictionary", None) is not None:
+                    col.dictionary = src.dictionary
+                col.logical_dtype = src.dtype
+                out_cols[f"g__{name}"] = col
+                order_names.append((name, f"g__{name}"))
+            for call, col in zip(calls, acols):
+                name = call.toString()
+                out_cols[f"a__{name}"] = col
+                order_names.append((name, f"a__{name}"))
+            cc = ColumnContainer([n for n, _ in order_names],
+                                 dict(order_names))
+            cc = self.fix_column_to_row_type(cc, rel.getRowType())
+            return DataContainer(DeviceTable(out_cols), cc)
         oc, ov, on, G = runtime.hash_groupby(cols, n_rows,
                                              keyspecs, pred_prog, specs)
 
@@ -1881,9 +1908,12 @@ class DaskAggregatePlugin(BaseRelPlugin):
                 order_names.append((name, f"g__{name}"))
                 continue
             if len(ks) > 4 and ks[4] == 1:
-                # f64-bits key: value = bitcast(code-1); code 0 = NaN/NULL
+                # f64-bits key: value = bitcast(code-1); code 0 = NaN/NULL.
+                # code != 0, not code > 0: the code of a negative double has
+                # its top bit set and is negative as an i64
+                from dask_sql_amd.physical.rex import OP_NE_I64
                 prog = [(OP_COL, 0, 0), (OP_LIT_I64, 0, 0),
-                        (OP_GT_I64, 0, 0),
+                        (OP_NE_I64, 0, 0),
                         (OP_COL, 0, 0), (OP_LIT_I64, 0, 1), (OP_SUB_I64, 0, 0),
                         (OP_BITS_F64, 0, 0),
                         (OP_LIT_NULL, 0, 0), (OP_SELECT, 0, 0)]

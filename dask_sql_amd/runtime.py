@@ -89,6 +89,10 @@ class _AggSpec(ct.Structure):
     ]
 
 
+class _GbFinishCall(ct.Structure):
+    _fields_ = [("kind", ct.c_int32), ("agg", ct.c_int32)]
+
+
 _LIB = None
 
 
@@ -863,6 +867,76 @@ class Runtime:
             "dsx_hash_groupby",
         )
         return oc.value, ov.value, on.value, og.value
+
+    # finalize kinds of hash_groupby_cols (DsxGbFinishKind)
+    GB_FIN_KINDS = {"count": 0, "sum_i": 1, "sum_f": 2, "min_i": 3,
+                    "max_i": 4, "min_f": 5, "max_f": 6, "avg": 7}
+
+    def hash_groupby_cols(self, cols, n, keyspecs, pred_prog, agg_specs,
+                          calls):
+        """hash_groupby with the output columns finished in the same call
+        (dsx_hash_groupby_cols): calls = [(finalize kind name, index into
+        agg_specs)]. Returns ([key DeviceColumn], [call DeviceColumn],
+        n_groups); the columns own their buffers. Integer keys come back as
+        I64 with a validity buffer only when nullable, a float (mode 1) key
+        as F64 with one; COUNT as I64 without, every other call with."""
+        unsafe = any(
+            getattr(cols[spec[0]], "_keep_alive", None) is not None
+            and not getattr(cols[spec[0]], "_owner", True)
+            for spec in keyspecs)
+        ks = (_KeySpec * max(len(keyspecs), 1))()
+        for i, spec in enumerate(keyspecs):
+            ci, mn, rng, nullable = spec[:4]
+            ks[i].mode = spec[4] if len(spec) > 4 else 0
+            ks[i].col = ci
+            ks[i].min = mn
+            ks[i].range = rng
+            ks[i].nullable = 1 if nullable else 0
+        aggs = (_AggSpec * max(len(agg_specs), 1))()
+        for i, (op, prog) in enumerate(agg_specs):
+            parr, plen = prog
+            aggs[i].op = op
+            aggs[i].prog_len = plen
+            ct.memmove(aggs[i].prog, parr, plen * ct.sizeof(_Instr))
+        fc = (_GbFinishCall * max(len(calls), 1))()
+        for i, (kind, agg) in enumerate(calls):
+            fc[i].kind = self.GB_FIN_KINDS[kind]
+            fc[i].agg = agg
+        if pred_prog is not None:
+            pparr, pplen = pred_prog
+        else:
+            pparr, pplen = (_Instr * 1)(), 0
+        nout = len(keyspecs) + len(calls)
+        datas = (ct.c_void_p * max(nout, 1))()
+        valids = (ct.c_void_p * max(nout, 1))()
+        og = ct.c_int64()
+        if unsafe:
+            self.lib.dsx_gb_hist_cache_enable(self.ctx, 0)
+        try:
+            _check(
+                self.lib,
+                self.lib.dsx_hash_groupby_cols(
+                    self.ctx, self._cols_array(cols), ct.c_int(len(cols)),
+                    ct.c_int64(n), ks, ct.c_int(len(keyspecs)), pparr,
+                    ct.c_int(pplen), aggs, ct.c_int(len(agg_specs)), fc,
+                    ct.c_int(len(calls)), datas, valids, ct.byref(og)),
+                "dsx_hash_groupby_cols",
+            )
+        finally:
+            if unsafe:
+                self.lib.dsx_gb_hist_cache_enable(self.ctx, 1)
+        G = og.value
+        out = []
+        for i in range(nout):
+            if i < len(keyspecs):
+                spec = keyspecs[i]
+                dtype = F64 if (len(spec) > 4 and spec[4] == 1) else I64
+            else:
+                dtype = F64 if calls[i - len(keyspecs)][0] in (
+                    "sum_f", "min_f", "max_f", "avg") else I64
+            out.append(DeviceColumn(self, datas[i], valids[i] or None, G,
+                                    dtype, owner=True))
+        return out[:len(keyspecs)], out[len(keyspecs):], G
 
     def partition(self, codes: DeviceColumn, nbuckets, validity_ptr=None):
         """Returns (sel DeviceColumn-like ptr wrapped, offsets np.ndarray)."""

@@ -454,6 +454,50 @@ int dsx_hash_groupby(DsxCtx* ctx,
                      uint64_t** out_codes, void** out_vals /*[naggs][G]*/,
                      uint64_t** out_counts /*[naggs][G]*/, int64_t* out_groups);
 
+/* dsx_hash_groupby plus the finish of its output columns in the same call:
+ * the group keys unpacked from the packed code and every aggregate call
+ * finalized, all written by ONE kernel launch once G is known (the reference
+ * does this step on the grouped frame, aggregate.py:575-581 reset_index and
+ * the per-call finalizers). Same three paths and fallbacks as
+ * dsx_hash_groupby.
+ *
+ * Keys come back in `keys` order: mode 0 as i64 = (code / stride) % space
+ * (− 1 when nullable, slot 0 = NULL) + min, with a validity buffer only when
+ * the key is nullable; mode 1 as f64 = bitcast(code − 1), code 0 = NULL (cell
+ * holds NaN), always with a validity buffer.
+ * Calls: `agg` indexes `aggs` (one accumulator per call; the library maps it
+ * to the partition path's value slot, which skips COUNT accumulators).
+ * COUNT is i64 with no validity buffer. Every other kind has one and is NULL
+ * when the non-NULL input count is 0 (f64 cells then hold NaN, i64 cells 0):
+ * SUM_I/MIN_I/MAX_I are i64, SUM_F/MIN_F/MAX_F f64, AVG f64 = sum / count
+ * over a DSX_AGG_SUM_F64 accumulator.
+ * out_datas/out_valids: caller arrays of nkeys + ncalls slots (keys first),
+ * filled with pool allocations (free with dsx_free); out_valids[i] is NULL
+ * where no validity buffer is due. nkeys must be ≥ 1. The call returns with
+ * the finish kernel queued on the context's stream, not completed. */
+enum DsxGbFinishKind {
+  DSX_GB_FIN_COUNT = 0,
+  DSX_GB_FIN_SUM_I = 1,
+  DSX_GB_FIN_SUM_F = 2,
+  DSX_GB_FIN_MIN_I = 3,
+  DSX_GB_FIN_MAX_I = 4,
+  DSX_GB_FIN_MIN_F = 5,
+  DSX_GB_FIN_MAX_F = 6,
+  DSX_GB_FIN_AVG = 7,
+};
+typedef struct DsxGbFinishCall {
+  int32_t kind;  /* DsxGbFinishKind */
+  int32_t agg;   /* index into aggs */
+} DsxGbFinishCall;
+int dsx_hash_groupby_cols(DsxCtx* ctx,
+                          const DsxColumn* cols, int ncols, int64_t n,
+                          const DsxKeySpec* keys, int nkeys,
+                          const DsxInstr* pred, int pred_len,
+                          const DsxAggSpec* aggs, int naggs,
+                          const DsxGbFinishCall* calls, int ncalls,
+                          void** out_datas, uint8_t** out_valids,
+                          int64_t* out_groups);
+
 /* ---- shuffle support --------------------------------------- */
 
 /* replaces dask's hash-repartition "tasks" shuffle split
