@@ -4148,6 +4148,7 @@ void jit_cache_destroy(DsxCtx* c) {
 #include "radix_sort.inc"
 #include "window.inc"
 #include "window_rows.inc"
+#include "window_words.inc"
 
 // ---------------------------------------------------------------------------
 // dsx_jit_expr_source — TEST INFRASTRUCTURE: emit the JIT expression

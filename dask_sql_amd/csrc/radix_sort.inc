@@ -42,6 +42,21 @@ __device__ __forceinline__ void rsort_count(uint32_t* s_bins, uint32_t dg,
   }
 }
 
+// the word's u64 order code of row r: one float key (fcol >= 0) or the
+// packed integer-kind keys. Shared with k_win_mark_word (window_words.inc),
+// which must tell rows apart exactly where the sort does.
+__device__ __forceinline__ uint64_t rsort_word_code(const ColsArg& C,
+                                                    const KeyArg& K, int fcol,
+                                                    int fmode, int64_t r) {
+  if (fcol >= 0) {
+    Slot v;
+    bool valid;
+    vm_load_col(C, fcol, r, v, valid);
+    return dsx_f64_order_code(v.f, valid ? 1 : 0, fmode);
+  }
+  return pack_key(K, C, r);
+}
+
 __global__ void __launch_bounds__(BLOCK) k_rsort_codes(
     ColsArg C, int64_t n, const KeyArg* Kp, int fcol, int fmode,
     const uint32_t* perm_in, uint64_t* code_out, uint32_t* rid_out,
@@ -61,14 +76,7 @@ __global__ void __launch_bounds__(BLOCK) k_rsort_codes(
     uint64_t code = 0;
     if (active) {
       uint32_t r = perm_in ? perm_in[i] : (uint32_t)i;
-      if (fcol >= 0) {
-        Slot v;
-        bool valid;
-        vm_load_col(C, fcol, (int64_t)r, v, valid);
-        code = dsx_f64_order_code(v.f, valid ? 1 : 0, fmode);
-      } else {
-        code = pack_key(*Kp, C, (int64_t)r);
-      }
+      code = rsort_word_code(C, *Kp, fcol, fmode, (int64_t)r);
       code_out[i] = code;
       rid_out[i] = r;
     }
@@ -171,6 +179,17 @@ __global__ void __launch_bounds__(BLOCK) k_rsort_scatter(
   }
 }
 
+// launch grid of the row passes; DSX_RSORT_GRID caps it (read per call —
+// the test knob that lets a small input make one block walk several tiles)
+static int rsort_grid(int64_t n) {
+  int grid = (int)min((int64_t)MAX_GRID, (n + BLOCK - 1) / BLOCK);
+  if (const char* e = getenv("DSX_RSORT_GRID")) {
+    int g = atoi(e);
+    if (g >= 1 && g < grid) grid = g;
+  }
+  return grid;
+}
+
 struct RsortBufs {
   void* code[2] = {nullptr, nullptr};
   void* rid[2] = {nullptr, nullptr};
@@ -179,11 +198,7 @@ struct RsortBufs {
 static int rsort_run(DsxCtx* c, const ColsArg& C, const KeyArg& K, int fcol,
                      int fmode, int64_t n, const uint32_t* perm_in,
                      RsortBufs& B, uint32_t* out_perm) {
-  int grid = (int)min((int64_t)MAX_GRID, (n + BLOCK - 1) / BLOCK);
-  if (const char* e = getenv("DSX_RSORT_GRID")) {  // read per call (tests)
-    int g = atoi(e);
-    if (g >= 1 && g < grid) grid = g;
-  }
+  int grid = rsort_grid(n);
   const int nb = RSORT_RADIX;
   const int64_t hist_b = (int64_t)grid * nb * 8;
   const int64_t dig_b = RSORT_DIGITS * RSORT_RADIX * 8;
@@ -263,17 +278,19 @@ static int rsort_run(DsxCtx* c, const ColsArg& C, const KeyArg& K, int fcol,
   return 0;
 }
 
-extern "C" int dsx_sort_word(DsxCtx* c, const DsxColumn* cols, int ncols,
-                             const DsxKeySpec* keys, int nkeys, int64_t n,
-                             const uint32_t* perm_in, uint32_t** out_perm) {
-  *out_perm = nullptr;
+// validates one word (dsx_sort_word's contract) and fills the kernel
+// arguments; -3 on a malformed spec, -4 on a key space above 2^62
+static int rsort_parse_word(const DsxColumn* cols, int ncols,
+                            const DsxKeySpec* keys, int nkeys, int64_t n,
+                            KeyArg& K, int& fcol, int& fmode, ColsArg& C) {
   if (ncols < 1 || ncols > DSX_MAX_COLS || nkeys < 1 || nkeys > DSX_MAX_KEYS)
     FAIL(-3, "sort word spec");
   if (n < 0 || n > 0xFFFFFFFEll)
     FAIL(-3, "sort too large for u32 row ids");
-  KeyArg K{};
+  K = KeyArg{};
   K.nkeys = nkeys;
-  int fcol = -1, fmode = 0;
+  fcol = -1;
+  fmode = 0;
   uint64_t space = 1;
   for (int j = 0; j < nkeys; j++) {
     if (keys[j].col < 0 || keys[j].col >= ncols)
@@ -296,15 +313,27 @@ extern "C" int dsx_sort_word(DsxCtx* c, const DsxColumn* cols, int ncols,
     if (space > (1ull << 62) / range) FAIL(-4, "sort key space > 2^62");
     space *= range;
   }
-  if (n == 0) return pool_alloc(c, 4, (void**)out_perm);
-  ColsArg C{};
+  C = ColsArg{};
   C.ncols = ncols;
   for (int i = 0; i < ncols; i++) {
     C.data[i] = cols[i].data;
     C.validity[i] = cols[i].validity;
     C.dtype[i] = cols[i].dtype;
   }
-  int rc = pool_alloc(c, n * 4, (void**)out_perm);
+  return 0;
+}
+
+extern "C" int dsx_sort_word(DsxCtx* c, const DsxColumn* cols, int ncols,
+                             const DsxKeySpec* keys, int nkeys, int64_t n,
+                             const uint32_t* perm_in, uint32_t** out_perm) {
+  *out_perm = nullptr;
+  KeyArg K;
+  ColsArg C;
+  int fcol, fmode;
+  int rc = rsort_parse_word(cols, ncols, keys, nkeys, n, K, fcol, fmode, C);
+  if (rc) return rc;
+  if (n == 0) return pool_alloc(c, 4, (void**)out_perm);
+  rc = pool_alloc(c, n * 4, (void**)out_perm);
   if (rc) return rc;
   RsortBufs B;
   rc = rsort_run(c, C, K, fcol, fmode, n, perm_in, B, *out_perm);

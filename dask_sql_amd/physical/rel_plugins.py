@@ -2724,10 +2724,20 @@ class DaskWindowPlugin(BaseRelPlugin):
       _device_rows → dsx_window_rows (LDS tile pass for narrow bounded
       frames, per-partition scans + prefix differences otherwise). They
       fall back to the host rolling restatement (_frame_apply) when
-      DSX_DISABLE_DEVWINDOW is set, an order key is explicitly NULLS
-      FIRST, a key is not an integer kind or does not pack, sort_perm
-      refuses, the value column is dictionary-encoded, or a bounded
-      MIN/MAX frame is wider than window_frames.WIN_ROWS_TILE_MAXW."""
+      DSX_DISABLE_DEVWINDOW is set, a key dtype is not device-sortable,
+      a single integer key spans more than 2^62, the value column is
+      dictionary-encoded, or a bounded MIN/MAX frame is wider than
+      window_frames.WIN_ROWS_TILE_MAXW.
+
+    The device paths share the sort front half _device_sort_keys: the
+    bucket sort + keypack codes for integer-kind keys that pack, the
+    sort_word chain + boundary marks + segment ids (_word_sort_keys) for
+    float keys, explicit NULLS FIRST, skew, more than 4 keys, key spaces
+    above 2^62 and tables wider than 16 columns. Knobs, read per call:
+    DSX_DISABLE_DEVWINDOW (ordered and framed windows on the host),
+    DSX_DISABLE_WINWORDS=1 (no word front half: those shapes run on the
+    host as they did before it existed), DSX_WIN_WORDS=1 (every device
+    window through the word front half; for A/B runs)."""
 
     class_name = "Window"
 
@@ -2753,9 +2763,12 @@ class DaskWindowPlugin(BaseRelPlugin):
     _AGGS = {"sum", "count", "avg", "min", "max"}
 
     def _one(self, runtime, cols, n, spec):
-        if any(nf is True for nf in getattr(spec, "order_nf", [])):
-            # explicit NULLS FIRST on a window order key: host sort path
-            # honors per-key placement
+        import os as _os
+        if any(nf is True for nf in getattr(spec, "order_nf", [])) \
+                and _os.environ.get("DSX_DISABLE_WINWORDS", "0") == "1":
+            # explicit NULLS FIRST on a window order key is sorted by the
+            # word chain only (_device_sort_keys); with that off, the host
+            # sort path honors per-key placement
             return self._host_ordered(runtime, cols, n, spec)
         if getattr(spec, "frame", None) is None \
                 and spec.func == "last_value" and spec.order_idx \
@@ -2846,30 +2859,134 @@ class DaskWindowPlugin(BaseRelPlugin):
 
     def _device_sort_keys(self, runtime, cols, n, spec, need_full=True):
         """Shared front half of the device window paths: the sort
-        permutation over (partition, order) keys plus the partition codes
-        (and, with need_full, the partition+order peer codes) gathered into
-        sorted order. None when a key is not an integer kind, the key space
-        does not pack, or sort_perm refuses → host fallback."""
+        permutation over (partition, order) keys plus, gathered into sorted
+        order, per-row partition ids and (with need_full) partition+order
+        peer ids — any u64 arrays whose adjacent values differ exactly at a
+        boundary. Two ways to get them:
+
+        - _bucket_sort_keys: sort_perm + keypack codes, for integer-kind
+          keys that pack into one code;
+        - _word_sort_keys: the sort_word chain + boundary marks, for
+          whatever the first declines (float keys, skew, more than 4 keys,
+          key spaces above 2^62, tables wider than 16 columns) and for an
+          explicit NULLS FIRST order key.
+
+        DSX_DISABLE_WINWORDS=1 turns the second off (those shapes run on
+        the host again); DSX_WIN_WORDS=1 sends every shape through it.
+        Both are read per call. None → host fallback."""
+        import os as _os
+        words_on = _os.environ.get("DSX_DISABLE_WINWORDS", "0") != "1"
+        force_words = words_on and \
+            _os.environ.get("DSX_WIN_WORDS", "0") == "1"
+        nulls_first = any(nf is True
+                          for nf in getattr(spec, "order_nf", []))
+        if not force_words and not nulls_first:
+            keys = self._bucket_sort_keys(runtime, cols, n, spec, need_full)
+            if keys is not None:
+                return keys
+        if not words_on:
+            return None
+        return self._word_sort_keys(runtime, cols, n, spec, need_full)
+
+    @staticmethod
+    def _window_key(runtime, cols, work, n, i, want_rank):
+        """Key column i as the device sorts it: a dictionary ORDER BY key
+        goes through its alphabetic rank LUT (appended to `work`)."""
+        col = cols[i]
+        if getattr(col, "dictionary", None) is not None and want_rank:
+            order = sorted(
+                (j for j, s_ in enumerate(col.dictionary)
+                 if s_ is not None),
+                key=lambda j: col.dictionary[j])
+            rank = np.zeros(len(col.dictionary), dtype=np.int64)
+            for r_, j in enumerate(order):
+                rank[j] = r_
+            lut = runtime.upload_column(rank)
+            g = runtime.gather(lut, col.data, n)
+            ranked = rt.DeviceColumn(runtime, g.data, col.validity, n,
+                                     rt.I64, owner=False,
+                                     keep_alive=(g, col, lut))
+            work.append(ranked)
+            return len(work) - 1, ranked
+        return i, col
+
+    @staticmethod
+    def _zero_ids(runtime, n):
+        """Constant zero ids for "no partition key": an eval of literal 0
+        over n rows."""
+        from dask_sql_amd.physical.rex import OP_LIT_I64
+        z = runtime.upload_column(np.zeros(1, dtype=np.int64))
+        return runtime.eval(runtime.make_prog([(OP_LIT_I64, 0, 0)]), [z], n,
+                            rt.I64, with_validity=False)
+
+    def _word_sort_keys(self, runtime, cols, n, spec, need_full=True):
+        """Word front half: plan_window_words cuts the (partition, order)
+        keys into 64-bit words, sort_word runs them least significant
+        first, window_mark_word ORs each word's boundary marks over the
+        sorted sequence and window_seg_ids turns marks into ids — the
+        partition words' marks give the partition ids, the order words'
+        marks on top of them the peer ids. Each word brings only its own
+        columns. None (→ host) when a key dtype is not device-sortable or
+        a word is refused (one integer key spanning more than 2^62)."""
+        from dask_sql_amd.physical.sort_words import (plan_window_words,
+                                                      window_order_mode)
+        work = list(cols)
+
+        def key_rec(i, want_rank, mode):
+            ki, col = self._window_key(runtime, cols, work, n, i, want_rank)
+            if col.dtype in (rt.F64, rt.F32):
+                return (ki, True, 0, 0, bool(col.validity), mode)
+            if col.dtype not in _INT_KINDS:
+                return None
+            mn, mx, nn = _minmax_cached(runtime, col)
+            if nn == 0:
+                mn, mx = 0, 0
+            return (ki, False, mn, mx - mn + 1, bool(col.validity), mode)
+
+        nfs = list(getattr(spec, "order_nf", [])) or \
+            [None] * len(spec.order_idx)
+        part = [key_rec(i, False, 0) for i in spec.part_idx]
+        order = [key_rec(i, True, window_order_mode(desc, nf))
+                 for (i, desc), nf in zip(spec.order_idx, nfs)]
+        if any(k is None for k in part + order) or not part + order:
+            return None
+        words = plan_window_words(part, order)
+        perm = None
+        for w in words:
+            perm = runtime.sort_word([work[i] for i in w.cols],
+                                     list(w.specs), n, perm)
+            if perm is None:
+                return None
+
+        def mark(side, marks):
+            for w in words:
+                if w.is_partition == side:
+                    marks = runtime.window_mark_word(
+                        [work[i] for i in w.cols], list(w.specs), n, perm,
+                        marks)
+                    if marks is None:
+                        # validated exactly like the sort_word call above
+                        raise rt.DsxError("window_mark_word refused a word "
+                                          "that sort_word accepted")
+            return marks
+
+        marks = mark(True, None)
+        ps = runtime.window_seg_ids(marks, n)[0] if part \
+            else self._zero_ids(runtime, n)
+        fs = ps
+        if order and need_full:
+            # ORed into the same buffer: ps is already computed from it
+            fs = runtime.window_seg_ids(mark(False, marks), n)[0]
+        return perm, ps, fs
+
+    def _bucket_sort_keys(self, runtime, cols, n, spec, need_full=True):
+        """Bucket front half: sort_perm over the packed (partition, order)
+        keys, keypack codes as the ids. None when a key is not an integer
+        kind, the key space does not pack, or sort_perm refuses."""
         work = list(cols)
 
         def key_of(i, want_rank):
-            col = cols[i]
-            if getattr(col, "dictionary", None) is not None and want_rank:
-                order = sorted(
-                    (j for j, s_ in enumerate(col.dictionary)
-                     if s_ is not None),
-                    key=lambda j: col.dictionary[j])
-                rank = np.zeros(len(col.dictionary), dtype=np.int64)
-                for r_, j in enumerate(order):
-                    rank[j] = r_
-                lut = runtime.upload_column(rank)
-                g = runtime.gather(lut, col.data, n)
-                ranked = rt.DeviceColumn(runtime, g.data, col.validity, n,
-                                         rt.I64, owner=False,
-                                         keep_alive=(g, col, lut))
-                work.append(ranked)
-                return len(work) - 1, ranked
-            return i, col
+            return self._window_key(runtime, cols, work, n, i, want_rank)
 
         part, order = [], []
         for i in spec.part_idx:
@@ -2901,13 +3018,7 @@ class DaskWindowPlugin(BaseRelPlugin):
 
         def packed(specs):
             if not specs:
-                z = runtime.upload_column(np.zeros(1, dtype=np.int64))
-                # constant zero code for "no partition": broadcastless —
-                # use an eval of literal 0 over n rows instead
-                from dask_sql_amd.physical.rex import OP_LIT_I64
-                return runtime.eval(
-                    runtime.make_prog([(OP_LIT_I64, 0, 0)]), [z], n,
-                    rt.I64, with_validity=False)
+                return self._zero_ids(runtime, n)
             codes, _sp = runtime.keypack(
                 work, [(ki, mn, rng, nf) for (ki, mn, rng, nf, _m)
                        in specs], n)

@@ -7,6 +7,10 @@ the whole collation — the reference's own procedure, key by key from the
 last to the first with a stable sort (physical/utils/sort.py:36-60), with
 several keys per step where they fit one code.
 
+A window's PARTITION BY / ORDER BY keys are cut the same way by
+plan_window_words, partition and order keys in words of their own, so that
+Runtime.window_mark_word can tell a partition boundary from a peer boundary.
+
 Pure Python, no GPU: the plan is testable on its own.
 """
 from __future__ import annotations
@@ -28,6 +32,14 @@ class SortWord(NamedTuple):
            (the word's last ORDER BY key first, on stride 1)."""
     cols: tuple
     specs: tuple
+
+
+class WindowWord(NamedTuple):
+    """One word of a window's (partition, order) sort: a SortWord plus
+    which side of the OVER clause its keys come from."""
+    cols: tuple
+    specs: tuple
+    is_partition: bool
 
 
 def _emit(group):
@@ -87,3 +99,35 @@ def plan_sort_words(keys):
         words.append(_emit(group))
     words.reverse()
     return words
+
+
+PARTITION_MODE = 4    # ascending, NULLS LAST — how the host sorts partitions
+
+
+def window_order_mode(desc, nulls_first):
+    """DsxKeySpec mode of a window ORDER BY key: bit 2 = DESC; bit 4 =
+    NULLS LAST unless the key is explicitly NULLS FIRST (nulls_first is
+    True) — the host path places NULLs last for both directions when the
+    query does not say."""
+    return (2 if desc else 0) | (0 if nulls_first is True else 4)
+
+
+def plan_window_words(part_keys, order_keys):
+    """The sort_word chain of a window: rows sorted by the partition keys,
+    then the order keys, with every word tagged by the side it belongs to.
+
+    part_keys, order_keys: key lists in the plan_sort_words format, most
+    significant first. Order keys carry window_order_mode(); partition keys
+    are always taken with PARTITION_MODE, whatever mode they carry.
+
+    Returns WindowWords LEAST significant first — plan_sort_words(order_keys)
+    followed by plan_sort_words(part_keys). A word never mixes the two
+    sides: the OR of the partition words' boundary marks (Runtime.
+    window_mark_word) is then exactly the partition boundaries, and the
+    order words' marks on top of them the peer boundaries."""
+    part_keys = [(c, f, mn, rng, nullable, PARTITION_MODE)
+                 for c, f, mn, rng, nullable, _mode in part_keys]
+    return [WindowWord(w.cols, w.specs, False)
+            for w in plan_sort_words(order_keys)] + \
+           [WindowWord(w.cols, w.specs, True)
+            for w in plan_sort_words(part_keys)]

@@ -269,7 +269,7 @@ class Runtime:
         self.lib.dsx_prof_reset(self.ctx)
 
     def prof_get(self) -> dict:
-        cap = 32
+        cap = 64  # more than the library has kernel families
         names = ((ct.c_char * 32) * cap)()
         ms = (ct.c_double * cap)()
         launches = (ct.c_int64 * cap)()
@@ -749,6 +749,56 @@ class Runtime:
             return None
         _check(self.lib, rc, "dsx_sort_word")
         return DeviceColumn(self, perm.value, None, n, I32, owner=True)
+
+    def window_mark_word(self, cols, keyspecs, n, perm, marks=None):
+        """Boundary marks of one order word over sorted positions
+        (dsx_window_mark_word): mark[i] = i == 0 or the word's code of row
+        perm[i] differs from that of row perm[i-1]. cols / keyspecs as for
+        sort_word; perm: DeviceColumn of u32 row ids (None = identity).
+        marks=None returns a new u8 DeviceColumn; a given one is ORed into
+        and returned. None on -3/-4 (unsupported → host)."""
+        nk = len(keyspecs)
+        ks = (_KeySpec * max(nk, 1))()
+        for i, spec in enumerate(keyspecs):
+            ks[i].col = spec[0]
+            ks[i].min = spec[1]
+            ks[i].range = spec[2]
+            ks[i].nullable = 1 if spec[3] else 0
+            ks[i].mode = spec[4]
+        for what, col in (("perm", perm), ("marks", marks)):
+            if col is not None and col.len != n:
+                raise DsxError(f"window_mark_word: {what} has {col.len} "
+                               f"entries, expected {n}")
+        m = ct.c_void_p(marks.data if marks is not None else None)
+        rc = self.lib.dsx_window_mark_word(
+            self.ctx, self._cols_array(cols), ct.c_int(len(cols)), ks,
+            ct.c_int(nk), ct.c_int64(n),
+            ct.c_void_p(perm.data) if perm is not None else None,
+            ct.byref(m))
+        if rc in (-3, -4):
+            return None
+        _check(self.lib, rc, "dsx_window_mark_word")
+        if marks is not None:
+            return marks
+        return DeviceColumn(self, m.value, None, n, BOOL8, owner=True)
+
+    def window_seg_ids(self, marks, n):
+        """Segment ids of sorted positions from boundary marks
+        (dsx_window_seg_ids): ids[i] = marks set in [0, i], minus one — a
+        drop-in for the sorted key codes window_ordered / window_rows take.
+        Returns (DeviceColumn of n u64 ids, number of segments)."""
+        if marks.len != n:
+            raise DsxError(f"window_seg_ids: marks has {marks.len} "
+                           f"entries, expected {n}")
+        ids = ct.c_void_p()
+        nseg = ct.c_int64()
+        _check(self.lib,
+               self.lib.dsx_window_seg_ids(
+                   self.ctx, ct.c_void_p(marks.data), ct.c_int64(n),
+                   ct.byref(ids), ct.byref(nseg)),
+               "dsx_window_seg_ids")
+        return (DeviceColumn(self, ids.value, None, n, I64, owner=True),
+                nseg.value)
 
     WIN_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "lag": 3,
                  "lead": 4, "first_value": 5, "sum": 6, "count": 7,

@@ -405,6 +405,36 @@ int dsx_window_rows(DsxCtx* ctx, const uint32_t* perm, int64_t n,
                     int out_dtype, void** out_data, uint8_t** out_valid,
                     int want_valid);
 
+/* Boundary marks of ONE order word over a sorted row sequence — the window
+ * front half for keys that do not pack into one code (float keys, more than
+ * DSX_MAX_KEYS keys, key spaces above 2^62; reference rel/logical/
+ * window.py:212-428 groups the sorted frame with groupby(dropna=False)).
+ * The word is specified and validated exactly as dsx_sort_word takes it
+ * (same -3 / -4 answers, same code: pack_key or csrc/sort_code.h, so NULL
+ * and NaN share a slot and -0.0 ties with +0.0). For sorted position i,
+ *   mark[i] = (i == 0) || code(perm[i]) != code(perm[i-1])
+ * with perm NULL = identity. *marks_inout NULL: the library allocates u8[n]
+ * (free with dsx_free) and writes the marks; otherwise the marks are ORed
+ * into the given buffer, so the boundaries of a multi-word key are the OR
+ * over its words. n == 0 is legal. On failure nothing stays allocated and
+ * *marks_inout is NULL (a buffer the caller passed in stays the caller's).
+ * DSX_RSORT_GRID caps the launch grid as for dsx_sort_word. */
+int dsx_window_mark_word(DsxCtx* ctx, const DsxColumn* cols, int ncols,
+                         const DsxKeySpec* keys, int nkeys, int64_t n,
+                         const uint32_t* perm /* nullable = identity */,
+                         uint8_t** marks_inout);
+
+/* Segment ids from boundary marks: ids[i] = (number of non-zero marks in
+ * [0, i]) - 1, library-allocated u64[n] (free with dsx_free) — adjacent
+ * values differ exactly at a mark, so the ids serve as pcode_sorted /
+ * fcode_sorted of dsx_window_ordered and dsx_window_rows. *out_segments
+ * (nullable) receives the number of marks. Three bounded phases (per-block
+ * counts, one-block scan, apply); no block waits on another. n == 0 is
+ * legal. On failure nothing stays allocated and *out_ids is NULL.
+ * DSX_RSORT_GRID caps the launch grid. */
+int dsx_window_seg_ids(DsxCtx* ctx, const uint8_t* marks, int64_t n,
+                       uint64_t** out_ids, int64_t* out_segments);
+
 /* ---- hash groupby-aggregate --------------------------------------------- */
 
 enum DsxAggOp {  /* reference AGGREGATION_MAPPING aggregate.py:117-231 subset:
