@@ -14,6 +14,7 @@ from dask_sql_amd import runtime as rt
 from dask_sql_amd.datacontainer import (ColumnContainer, DataContainer,
                                         DeferredFilter, DeviceTable,
                                         HostDataContainer)
+from dask_sql_amd.physical import keys
 from dask_sql_amd.physical.convert import BaseRelPlugin, RelConverter
 from dask_sql_amd.physical.rex import (KB, KF, KI, OP_AND, OP_COL,
                                        OP_IS_NOT_NULL, OP_NOT,
@@ -23,7 +24,7 @@ from dask_sql_amd.planner.plan import Call, InputRef
 
 logger = logging.getLogger(__name__)
 
-_INT_KINDS = (rt.I64, rt.I32, rt.I8, rt.BOOL8)
+_INT_KINDS = keys.INT_KINDS
 
 
 def _dicts_of(cols):
@@ -45,27 +46,6 @@ def _codes_i32(runtime, col):
     return runtime.upload_column(
         arr,
         None if valid is None else valid.astype(np.uint8), rt.I32)
-
-
-def _minmax_cached(runtime, col):
-    """Column statistics memo (the reference caches table statistics too —
-    datacontainer.py Statistics / statistics.py:21). Derived columns (gather
-    outputs) chain to their source via _stats_src: a subset's range is
-    bounded by its source's, so the PERSISTENT base column caches the range
-    across query steps (a superset range only widens the key space, never
-    changes results)."""
-    hit = getattr(col, "_minmax", None)
-    if hit is not None:
-        return hit
-    src = getattr(col, "_stats_src", None)
-    if src is not None and col.len > 0:
-        mn, mx, _ = _minmax_cached(runtime, src)
-        hit = (mn, mx, col.len)  # conservative: subset of source rows
-        col._minmax = hit
-        return hit
-    hit = runtime.minmax_i64(col)
-    col._minmax = hit
-    return hit
 
 
 def _gather_table(runtime, dc: DataContainer, sel_ptr, n_sel,
@@ -515,7 +495,7 @@ class DaskJoinPlugin(BaseRelPlugin):
             for ri in rhs_on:
                 col = rcols0[ri]
                 if col.validity:
-                    _, _, nn = _minmax_cached(runtime, col)
+                    _, _, nn = keys.minmax_cached(runtime, col)
                     if nn < dc_rhs.table.num_rows:
                         return self._empty_output(rel, runtime, dc_lhs,
                                                   cc_lhs)
@@ -897,17 +877,7 @@ class DaskJoinPlugin(BaseRelPlugin):
             if j in dense_ranges:
                 ranges.append(dense_ranges[j])
                 continue
-            lmn, lmx, lnn = _minmax_cached(runtime, lcols[li])
-            rmn, rmx, rnn = _minmax_cached(runtime, rcols[ri])
-            if lnn == 0 and rnn == 0:
-                mn, mx = 0, 0
-            elif lnn == 0:
-                mn, mx = rmn, rmx
-            elif rnn == 0:
-                mn, mx = lmn, lmx
-            else:
-                mn, mx = min(lmn, rmn), max(lmx, rmx)
-            ranges.append((mn, mx - mn + 1))
+            ranges.append(keys.joint_range(runtime, lcols[li], rcols[ri]))
 
         # build on the smaller side for INNER (what the reference gets from
         # dask's merge internals + JoinReorder, src/sql/optimizer/join_reorder.rs)
@@ -1008,17 +978,7 @@ class DaskJoinPlugin(BaseRelPlugin):
                                                     lhs_on, rhs_on)
         ranges = []
         for li, ri in zip(lhs_on, rhs_on):
-            lmn, lmx, lnn = _minmax_cached(runtime, lcols[li])
-            rmn, rmx, rnn = _minmax_cached(runtime, krcols[ri])
-            if lnn == 0 and rnn == 0:
-                mn, mx = 0, 0
-            elif lnn == 0:
-                mn, mx = rmn, rmx
-            elif rnn == 0:
-                mn, mx = lmn, lmx
-            else:
-                mn, mx = min(lmn, rmn), max(lmx, rmx)
-            ranges.append((mn, mx - mn + 1))
+            ranges.append(keys.joint_range(runtime, lcols[li], krcols[ri]))
         if swap:
             probe_dc, build_dc = kdc_rhs, dc_lhs
             probe_on, build_on = rhs_on, lhs_on
@@ -1143,17 +1103,7 @@ class DaskJoinPlugin(BaseRelPlugin):
                                                     lhs_on, rhs_on)
         ranges = []
         for li, ri in zip(lhs_on, rhs_on):
-            lmn, lmx, lnn = _minmax_cached(runtime, lcols[li])
-            rmn, rmx, rnn = _minmax_cached(runtime, krcols[ri])
-            if lnn == 0 and rnn == 0:
-                mn, mx = 0, 0
-            elif lnn == 0:
-                mn, mx = rmn, rmx
-            elif rnn == 0:
-                mn, mx = lmn, lmx
-            else:
-                mn, mx = min(lmn, rmn), max(lmx, rmx)
-            ranges.append((mn, mx - mn + 1))
+            ranges.append(keys.joint_range(runtime, lcols[li], krcols[ri]))
 
         if fprobe is not None:
             swap = fprobe == "r"
@@ -1699,11 +1649,8 @@ class DaskAggregatePlugin(BaseRelPlugin):
             if col.dtype not in _INT_KINDS:
                 raise RexCompileError(
                     "unsupported GROUP BY key dtype on GPU path")
-            mn, mx, nn = _minmax_cached(runtime, col)
-            if nn == 0:
-                mn, mx = 0, 0
-            nullable = bool(col.validity)
-            keyspecs.append((gi, mn, mx - mn + 1, nullable))
+            mn, rng = keys.key_range(runtime, col)
+            keyspecs.append((gi, mn, rng, bool(col.validity)))
         return keyspecs
 
     @staticmethod
@@ -2188,10 +2135,8 @@ class DaskAggregatePlugin(BaseRelPlugin):
         for call in calls:
             ai = agg.getArgs(call)[0].getIndex()
             ai = float_ids.get(ai, ai)
-            mn, mx, nn = _minmax_cached(runtime, cols[ai])
-            if nn == 0:
-                mn, mx = 0, 0
-            ks2 = keyspecs + [(ai, mn, mx - mn + 1, bool(cols[ai].validity))]
+            mn, rng = keys.key_range(runtime, cols[ai])
+            ks2 = keyspecs + [(ai, mn, rng, bool(cols[ai].validity))]
             pred_prog = runtime.make_prog([(OP_COL, filt_idx, 0)]) \
                 if filt_idx is not None else None
             oc, ov, on, G = runtime.hash_groupby(cols, dc.table.num_rows,
@@ -2376,23 +2321,32 @@ class DaskAggregatePlugin(BaseRelPlugin):
 
 class DaskSortPlugin(BaseRelPlugin):
     """ORDER BY (reference physical/utils/sort.py:9-60, pandas mergesort
-    per partition). Two device paths, then one gather per column:
+    per partition). convert sorts tables of at least DSX_SORT_MIN rows
+    through _device_sort and everything else, or whatever that declines,
+    with pandas on the host.
 
-    - all keys integer-kind (ints, dates, bools, dictionary strings through
-      their rank LUT): order-preserving packed codes → range partition →
+    _device_sort resolves every collation key once into a key record
+    (physical/keys.py owns that: a key's range, the rank column of a
+    dictionary string key, the dtypes the device sorts), adds the ORDER BY
+    mode bits (2 = DESC, 4 = NULLS LAST), and feeds one of two engines
+    from the same records, then gathers each column through the
+    permutation:
+
+    - all keys integer-kind (ints, dates, bools, ranked dictionary
+      strings): order-preserving packed codes → range partition →
       per-bucket LDS bitonic (dsx_sort_perm, stable via rowid tiebreak;
       VERDICT r1 #6);
     - any float key, or dsx_sort_perm declining (skew-overloaded bucket,
       key space > 2^62, more than 4 keys, a table wider than 16 columns):
-      the radix chain — plan_sort_words cuts the collation into 64-bit
-      words and dsx_sort_word (stable LSD radix) runs them least
-      significant first.
+      the radix chain — plan_sort_words cuts the records into 64-bit
+      words and keys.run_words runs dsx_sort_word (stable LSD radix) over
+      them least significant first.
 
-    Host fallback only below DSX_SORT_MIN rows, for key dtypes the device
-    does not hold, or a single integer key spanning more than 2^62.
-    DSX_DISABLE_RADIXSORT=1 turns the chain off (float keys and whatever
-    dsx_sort_perm declines sort on the host again); DSX_SORT_RADIX=1 sends
-    all-integer collations to the chain as well. Both are read per call."""
+    It declines (→ host) key dtypes the device does not hold and a single
+    integer key spanning more than 2^62. DSX_DISABLE_RADIXSORT=1 turns the
+    chain off (float keys and whatever dsx_sort_perm declines sort on the
+    host again); DSX_SORT_RADIX=1 sends all-integer collations to the
+    chain as well. Both are read per call."""
 
     class_name = "Sort"
 
@@ -2418,66 +2372,27 @@ class DaskSortPlugin(BaseRelPlugin):
         import os as _os
         from dask_sql_amd.physical.sort_words import plan_sort_words
         runtime = context._get_runtime()
-        cols = dc.backend_cols()
-        work = list(cols)
-        specs = []
-        keys = []  # (col, is_float, min, range, nullable, mode) per key
+        work = list(dc.backend_cols())  # + rank columns of dictionary keys
         n = dc.table.num_rows
         use_radix = _os.environ.get("DSX_DISABLE_RADIXSORT", "0") != "1"
         force_radix = use_radix and \
             _os.environ.get("DSX_SORT_RADIX", "0") == "1"
-        any_float = False
+        recs = []
         for idx, asc, nulls_first in collation:
-            col = cols[idx]
-            use_idx = idx
-            if getattr(col, "dictionary", None) is not None:
-                # dictionary codes are unordered — remap through the
-                # alphabetic rank LUT (None ranks with NULL handling)
-                order = sorted(
-                    (i for i, s_ in enumerate(col.dictionary)
-                     if s_ is not None),
-                    key=lambda i: col.dictionary[i])
-                rank = np.zeros(len(col.dictionary), dtype=np.int64)
-                for r_, i in enumerate(order):
-                    rank[i] = r_
-                lut = runtime.upload_column(rank)
-                g = runtime.gather(lut, col.data, n)
-                ranked = rt.DeviceColumn(runtime, g.data, col.validity,
-                                         n, rt.I64, owner=False,
-                                         keep_alive=(g, col, lut))
-                work.append(ranked)
-                use_idx = len(work) - 1
-                col = ranked
             mode = (2 if not asc else 0) | (0 if nulls_first else 4)
-            if col.dtype in (rt.F64, rt.F32):
-                if not use_radix:
-                    return None  # float keys on host, as before the chain
-                any_float = True
-                keys.append((use_idx, True, 0, 0, bool(col.validity), mode))
-                continue
-            elif col.dtype not in _INT_KINDS:
-                return None
-            mn, mx, nn = _minmax_cached(runtime, col)
-            if nn == 0:
-                mn, mx = 0, 0
-            specs.append((use_idx, mn, mx - mn + 1,
-                          bool(col.validity), mode))
-            keys.append((use_idx, False, mn, mx - mn + 1,
-                         bool(col.validity), mode))
+            rec = keys.key_record(runtime, work, n, idx, mode, rank=True)
+            if rec is None or (rec[1] and not use_radix):
+                return None  # float keys on host, as before the chain
+            recs.append(rec)
         perm = None
-        if not any_float and not force_radix:
+        if not force_radix and not any(rec[1] for rec in recs):
             # first ORDER BY key → highest stride: pass reversed
-            perm = runtime.sort_perm(work, list(reversed(specs)), n)
-            if perm is None and not use_radix:
-                return None
+            perm = runtime.sort_perm(
+                work, [keys.bucket_spec(rec) for rec in reversed(recs)], n)
+        if perm is None and use_radix:
+            perm = keys.run_words(runtime, plan_sort_words(recs), work, n)
         if perm is None:
-            # stable radix chain, least significant word first; each word
-            # brings only its own key columns
-            for w in plan_sort_words(keys):
-                perm = runtime.sort_word([work[i] for i in w.cols],
-                                         list(w.specs), n, perm)
-                if perm is None:
-                    return None
+            return None
         cc = dc.column_container
         out_cols = {}
         for f in cc.columns:
@@ -2709,35 +2624,41 @@ def _topk(pdf, keys, k):
 
 class DaskWindowPlugin(BaseRelPlugin):
     """reference rel/logical/window.py:212-428 (OverOperation dispatch +
-    map_on_each_group over sorted partitions). Two paths:
+    map_on_each_group over sorted partitions). _one routes each window
+    column to one of three device paths:
 
     - unordered partition aggregates (SUM/COUNT/AVG/MIN/MAX OVER
-      (PARTITION BY …)): all-device — fused groupby, hash join-back of the
+      (PARTITION BY …)), _device_agg: fused groupby, hash join-back of the
       per-group value, and a row scatter into original order;
-    - ranking and ordered (running, RANGE-peers default frame) aggregates:
-      the REFERENCE computes these in pandas per partition
-      (window.py:266-427 map_on_each_group); we restate the same pandas
-      computation on host over the key columns, then upload the one result
-      column. Parity-first; a device sort is a round-2+ widening;
+    - ranking, LAG/LEAD/FIRST_VALUE and ordered (running, RANGE-peers
+      default frame) aggregates, _device_ordered: the sort front half,
+      then dsx_window_ordered (binary-search ranks / shifts,
+      per-partition running scans with peer broadcast);
     - explicit ROWS frames (SUM/COUNT/AVG/MIN/MAX/FIRST_VALUE/LAST_VALUE
-      over ROWS BETWEEN … AND … / ROWS k PRECEDING): device-side through
-      _device_rows → dsx_window_rows (LDS tile pass for narrow bounded
-      frames, per-partition scans + prefix differences otherwise). They
-      fall back to the host rolling restatement (_frame_apply) when
-      DSX_DISABLE_DEVWINDOW is set, a key dtype is not device-sortable,
-      a single integer key spans more than 2^62, the value column is
-      dictionary-encoded, or a bounded MIN/MAX frame is wider than
-      window_frames.WIN_ROWS_TILE_MAXW.
+      over ROWS BETWEEN … AND … / ROWS k PRECEDING), _device_rows: the
+      sort front half, then dsx_window_rows (LDS tile pass for narrow
+      bounded frames, per-partition scans + prefix differences
+      otherwise).
 
-    The device paths share the sort front half _device_sort_keys: the
-    bucket sort + keypack codes for integer-kind keys that pack, the
-    sort_word chain + boundary marks + segment ids (_word_sort_keys) for
-    float keys, explicit NULLS FIRST, skew, more than 4 keys, key spaces
-    above 2^62 and tables wider than 16 columns. Knobs, read per call:
-    DSX_DISABLE_DEVWINDOW (ordered and framed windows on the host),
-    DSX_DISABLE_WINWORDS=1 (no word front half: those shapes run on the
-    host as they did before it existed), DSX_WIN_WORDS=1 (every device
-    window through the word front half; for A/B runs)."""
+    What these decline runs as the reference computes it, in pandas per
+    partition on the host (_host_ordered, _frame_apply; window.py:266-427
+    map_on_each_group), and the one result column is uploaded:
+    DSX_DISABLE_DEVWINDOW set, a key dtype that is not device-sortable, a
+    single integer key spanning more than 2^62, a dictionary-encoded
+    value column, OVER () aggregates, or a bounded MIN/MAX frame wider
+    than window_frames.WIN_ROWS_TILE_MAXW.
+
+    The sort front half is _device_sort_keys. It resolves the
+    (partition, order) keys once into key records — physical/keys.py owns
+    a key's range, its rank column and the dtypes the device sorts — and
+    feeds either the bucket sort + keypack codes (_bucket_ids; integer-kind
+    keys that pack) or the sort_word chain + boundary marks + segment ids
+    (_word_ids; float keys, explicit NULLS FIRST, skew, more than 4 keys,
+    key spaces above 2^62, tables wider than 16 columns) from them. Knobs,
+    read per call: DSX_DISABLE_DEVWINDOW (ordered and framed windows on
+    the host), DSX_DISABLE_WINWORDS=1 (no word front half: those shapes
+    run on the host as they did before it existed), DSX_WIN_WORDS=1 (every
+    device window through the word front half; for A/B runs)."""
 
     class_name = "Window"
 
@@ -2859,56 +2780,57 @@ class DaskWindowPlugin(BaseRelPlugin):
 
     def _device_sort_keys(self, runtime, cols, n, spec, need_full=True):
         """Shared front half of the device window paths: the sort
-        permutation over (partition, order) keys plus, gathered into sorted
-        order, per-row partition ids and (with need_full) partition+order
-        peer ids — any u64 arrays whose adjacent values differ exactly at a
-        boundary. Two ways to get them:
+        permutation over (partition, order) keys plus, in sorted order,
+        per-row partition ids and (with need_full) partition+order peer
+        ids — any u64 arrays whose adjacent values differ exactly at a
+        boundary. The keys are resolved once (keys.key_record; dictionary
+        ORDER BY keys through their rank column, PARTITION BY keys by raw
+        code) and the records feed either engine:
 
-        - _bucket_sort_keys: sort_perm + keypack codes, for integer-kind
-          keys that pack into one code;
-        - _word_sort_keys: the sort_word chain + boundary marks, for
-          whatever the first declines (float keys, skew, more than 4 keys,
-          key spaces above 2^62, tables wider than 16 columns) and for an
+        - _bucket_ids: sort_perm + keypack codes, for integer-kind keys
+          that pack into one code;
+        - _word_ids: the sort_word chain + boundary marks, for whatever
+          the first declines (float keys, skew, more than 4 keys, key
+          spaces above 2^62, tables wider than 16 columns) and for an
           explicit NULLS FIRST order key.
 
         DSX_DISABLE_WINWORDS=1 turns the second off (those shapes run on
         the host again); DSX_WIN_WORDS=1 sends every shape through it.
         Both are read per call. None → host fallback."""
         import os as _os
+        from dask_sql_amd.physical.sort_words import window_order_mode
         words_on = _os.environ.get("DSX_DISABLE_WINWORDS", "0") != "1"
         force_words = words_on and \
             _os.environ.get("DSX_WIN_WORDS", "0") == "1"
-        nulls_first = any(nf is True
-                          for nf in getattr(spec, "order_nf", []))
-        if not force_words and not nulls_first:
-            keys = self._bucket_sort_keys(runtime, cols, n, spec, need_full)
-            if keys is not None:
-                return keys
-        if not words_on:
+        nfs = list(getattr(spec, "order_nf", [])) or \
+            [None] * len(spec.order_idx)
+        try_bucket = not force_words and not any(nf is True for nf in nfs)
+        if not try_bucket and not words_on:
             return None
-        return self._word_sort_keys(runtime, cols, n, spec, need_full)
-
-    @staticmethod
-    def _window_key(runtime, cols, work, n, i, want_rank):
-        """Key column i as the device sorts it: a dictionary ORDER BY key
-        goes through its alphabetic rank LUT (appended to `work`)."""
-        col = cols[i]
-        if getattr(col, "dictionary", None) is not None and want_rank:
-            order = sorted(
-                (j for j, s_ in enumerate(col.dictionary)
-                 if s_ is not None),
-                key=lambda j: col.dictionary[j])
-            rank = np.zeros(len(col.dictionary), dtype=np.int64)
-            for r_, j in enumerate(order):
-                rank[j] = r_
-            lut = runtime.upload_column(rank)
-            g = runtime.gather(lut, col.data, n)
-            ranked = rt.DeviceColumn(runtime, g.data, col.validity, n,
-                                     rt.I64, owner=False,
-                                     keep_alive=(g, col, lut))
-            work.append(ranked)
-            return len(work) - 1, ranked
-        return i, col
+        # partition keys carry mode 0, which is the bucket route's;
+        # plan_window_words gives them PARTITION_MODE itself. Order keys:
+        # the host sorts them na_position="last" for BOTH directions
+        # (_host_ordered) unless the query says NULLS FIRST, which only
+        # the word route takes
+        wanted = [(i, 0, False) for i in spec.part_idx] + \
+            [(i, window_order_mode(desc, nf), True)
+             for (i, desc), nf in zip(spec.order_idx, nfs)]
+        work = list(cols)  # + rank columns of dictionary order keys
+        recs = []
+        for i, mode, rank in wanted:
+            rec = keys.key_record(runtime, work, n, i, mode, rank)
+            if rec is None or (rec[1] and not words_on):
+                return None
+            recs.append(rec)
+        part, order = recs[:len(spec.part_idx)], recs[len(spec.part_idx):]
+        want_fs = bool(order) and need_full
+        if try_bucket and not any(rec[1] for rec in recs):
+            out = self._bucket_ids(runtime, work, n, part, order, want_fs)
+            if out is not None:
+                return out
+        if not words_on or not recs:
+            return None
+        return self._word_ids(runtime, work, n, part, order, want_fs)
 
     @staticmethod
     def _zero_ids(runtime, n):
@@ -2919,44 +2841,20 @@ class DaskWindowPlugin(BaseRelPlugin):
         return runtime.eval(runtime.make_prog([(OP_LIT_I64, 0, 0)]), [z], n,
                             rt.I64, with_validity=False)
 
-    def _word_sort_keys(self, runtime, cols, n, spec, need_full=True):
+    def _word_ids(self, runtime, work, n, part, order, want_fs):
         """Word front half: plan_window_words cuts the (partition, order)
-        keys into 64-bit words, sort_word runs them least significant
-        first, window_mark_word ORs each word's boundary marks over the
-        sorted sequence and window_seg_ids turns marks into ids — the
-        partition words' marks give the partition ids, the order words'
-        marks on top of them the peer ids. Each word brings only its own
-        columns. None (→ host) when a key dtype is not device-sortable or
-        a word is refused (one integer key spanning more than 2^62)."""
-        from dask_sql_amd.physical.sort_words import (plan_window_words,
-                                                      window_order_mode)
-        work = list(cols)
-
-        def key_rec(i, want_rank, mode):
-            ki, col = self._window_key(runtime, cols, work, n, i, want_rank)
-            if col.dtype in (rt.F64, rt.F32):
-                return (ki, True, 0, 0, bool(col.validity), mode)
-            if col.dtype not in _INT_KINDS:
-                return None
-            mn, mx, nn = _minmax_cached(runtime, col)
-            if nn == 0:
-                mn, mx = 0, 0
-            return (ki, False, mn, mx - mn + 1, bool(col.validity), mode)
-
-        nfs = list(getattr(spec, "order_nf", [])) or \
-            [None] * len(spec.order_idx)
-        part = [key_rec(i, False, 0) for i in spec.part_idx]
-        order = [key_rec(i, True, window_order_mode(desc, nf))
-                 for (i, desc), nf in zip(spec.order_idx, nfs)]
-        if any(k is None for k in part + order) or not part + order:
-            return None
+        key records into 64-bit words, keys.run_words sorts by them,
+        window_mark_word ORs each word's boundary marks over the sorted
+        sequence and window_seg_ids turns marks into ids — the partition
+        words' marks give the partition ids, the order words' marks on top
+        of them the peer ids. Each word brings only its own columns. None
+        (→ host) when a word is refused (one integer key spanning more
+        than 2^62)."""
+        from dask_sql_amd.physical.sort_words import plan_window_words
         words = plan_window_words(part, order)
-        perm = None
-        for w in words:
-            perm = runtime.sort_word([work[i] for i in w.cols],
-                                     list(w.specs), n, perm)
-            if perm is None:
-                return None
+        perm = keys.run_words(runtime, words, work, n)
+        if perm is None:
+            return None
 
         def mark(side, marks):
             for w in words:
@@ -2974,67 +2872,35 @@ class DaskWindowPlugin(BaseRelPlugin):
         ps = runtime.window_seg_ids(marks, n)[0] if part \
             else self._zero_ids(runtime, n)
         fs = ps
-        if order and need_full:
+        if want_fs:
             # ORed into the same buffer: ps is already computed from it
             fs = runtime.window_seg_ids(mark(False, marks), n)[0]
         return perm, ps, fs
 
-    def _bucket_sort_keys(self, runtime, cols, n, spec, need_full=True):
+    def _bucket_ids(self, runtime, work, n, part, order, want_fs):
         """Bucket front half: sort_perm over the packed (partition, order)
-        keys, keypack codes as the ids. None when a key is not an integer
-        kind, the key space does not pack, or sort_perm refuses."""
-        work = list(cols)
-
-        def key_of(i, want_rank):
-            return self._window_key(runtime, cols, work, n, i, want_rank)
-
-        part, order = [], []
-        for i in spec.part_idx:
-            ki, col = key_of(i, False)
-            if col.dtype not in _INT_KINDS:
-                return None
-            part.append((ki, col, False))
-        for i, desc in spec.order_idx:
-            ki, col = key_of(i, True)
-            if col.dtype not in _INT_KINDS:
-                return None
-            order.append((ki, col, desc))
-
-        def spec_of(ki, col, desc, order_key):
-            mn, mx, nn = _minmax_cached(runtime, col)
-            if nn == 0:
-                mn, mx = 0, 0
-            mode = 0
-            if order_key:
-                # host sorts order keys na_position="last" for BOTH
-                # directions (_host_ordered)
-                mode = (2 if desc else 0) | 4
-            return (ki, mn, mx - mn + 1, bool(col.validity), mode)
-
-        sort_specs = [spec_of(*p, False) for p in part] +                      [spec_of(*o, True) for o in order]
-        perm = runtime.sort_perm(work, list(reversed(sort_specs)), n)
+        key records, keypack codes gathered into sorted order as the ids.
+        None when the key space does not pack or sort_perm refuses."""
+        recs = part + order
+        perm = runtime.sort_perm(
+            work, [keys.bucket_spec(rec) for rec in reversed(recs)], n)
         if perm is None:
             return None
 
-        def packed(specs):
-            if not specs:
+        def packed(recs):
+            if not recs:
                 return self._zero_ids(runtime, n)
-            codes, _sp = runtime.keypack(
-                work, [(ki, mn, rng, nf) for (ki, mn, rng, nf, _m)
-                       in specs], n)
-            return codes
+            return runtime.keypack(
+                work, [(ki, mn, rng, nullable) for
+                       (ki, _f, mn, rng, nullable, _m) in recs], n)[0]
 
-        pspecs = [spec_of(*p, False) for p in part]
-        fspecs = pspecs + [spec_of(*o, True) for o in order]
         try:
-            pcodes = packed(pspecs)
-            fcodes = packed(fspecs) if order and need_full \
-                else pcodes
+            pcodes = packed(part)
+            fcodes = packed(recs) if want_fs else pcodes
         except Exception:
-            return None  # key space overflow etc → host
+            return None  # key space overflow etc → next route
         ps = runtime.gather(pcodes, perm.data, n)
-        fs = runtime.gather(fcodes, perm.data, n) \
-            if order and need_full else ps
+        fs = runtime.gather(fcodes, perm.data, n) if want_fs else ps
         return perm, ps, fs
 
     def _device_ordered(self, runtime, cols, n, spec):
@@ -3144,10 +3010,8 @@ class DaskWindowPlugin(BaseRelPlugin):
         """groupby → per-group value → hash join-back → row scatter."""
         keyspecs = []
         for gi in spec.part_idx:
-            mn, mx, nn = _minmax_cached(runtime, cols[gi])
-            if nn == 0:
-                mn, mx = 0, 0
-            keyspecs.append((gi, mn, mx - mn + 1, bool(cols[gi].validity)))
+            mn, rng = keys.key_range(runtime, cols[gi])
+            keyspecs.append((gi, mn, rng, bool(cols[gi].validity)))
         arg = InputRef(spec.arg_idx, None) if spec.arg_idx is not None \
             else None
         speclist, fin = DaskAggregatePlugin()._agg_spec_expr(

@@ -346,6 +346,42 @@ class Runtime:
             arr[i] = c.c_struct()
         return arr
 
+    @staticmethod
+    def _keyspec_array(keyspecs):
+        """DsxKeySpec array of (col, min, range, nullable[, mode]) tuples;
+        a missing mode is 0. At least one element, so that an empty key
+        list still passes a valid pointer."""
+        ks = (_KeySpec * max(len(keyspecs), 1))()
+        for k, spec in zip(ks, keyspecs):
+            k.col = spec[0]
+            k.min = spec[1]
+            k.range = spec[2]
+            k.nullable = 1 if spec[3] else 0
+            if len(spec) > 4:
+                k.mode = spec[4]
+        return ks
+
+    @staticmethod
+    def _aggspec_array(agg_specs):
+        """DsxAggSpec array of (agg_op, prog) pairs."""
+        aggs = (_AggSpec * max(len(agg_specs), 1))()
+        for a, (op, (parr, plen)) in zip(aggs, agg_specs):
+            a.op = op
+            a.prog_len = plen
+            ct.memmove(a.prog, parr, plen * ct.sizeof(_Instr))
+        return aggs
+
+    @staticmethod
+    def _hist_cache_unsafe(cols, keyspecs):
+        """The C-side group-by hist cache keys on device pointers with
+        pool-free eviction; externally-backed key columns (torch/RCCL
+        staging) recycle pointers outside that hook — the cache is switched
+        off around a call over them."""
+        return any(
+            getattr(cols[spec[0]], "_keep_alive", None) is not None
+            and not getattr(cols[spec[0]], "_owner", True)
+            for spec in keyspecs)
+
     # ---- ops -------------------------------------------------------------
     def eval(self, prog, cols, n, out_dtype, with_validity=True) -> DeviceColumn:
         parr, plen = prog
@@ -472,16 +508,10 @@ class Runtime:
     def keypack(self, cols, keyspecs, n) -> tuple:
         """keyspecs: list of (col_idx, min, range, nullable).
         Returns (codes DeviceColumn(u64-as-i64), key_space)."""
-        ks = (_KeySpec * len(keyspecs))()
+        ks = self._keyspec_array(keyspecs)
         space = 1
-        for i, spec in enumerate(keyspecs):
-            ci, mn, rng, nullable = spec[:4]
-            ks[i].mode = spec[4] if len(spec) > 4 else 0
-            ks[i].col = ci
-            ks[i].min = mn
-            ks[i].range = rng
-            ks[i].nullable = 1 if nullable else 0
-            space *= rng + (1 if nullable else 0)
+        for spec in keyspecs:
+            space *= spec[2] + (1 if spec[3] else 0)
         out = self.empty_column(n, I64, False)
         _check(
             self.lib,
@@ -617,13 +647,7 @@ class Runtime:
         ordered pcols then bcols, n_out), or None when the build keys are
         not unique (nothing was allocated)."""
         parr, plen = prog
-        ks = (_KeySpec * len(keyspecs))()
-        for i, (ci, mn, rng, nullable) in enumerate(keyspecs):
-            ks[i].col = ci
-            ks[i].min = mn
-            ks[i].range = rng
-            ks[i].nullable = 1 if nullable else 0
-            ks[i].mode = 0
+        ks = self._keyspec_array(keyspecs)
         ncols = len(pcols) + len(bcols)
         datas = (ct.c_void_p * max(ncols, 1))()
         valids = (ct.c_void_p * max(ncols, 1))()
@@ -659,15 +683,8 @@ class Runtime:
         bucket overflow / unsupported shape (caller falls back to the
         flat-table join)."""
         nk = len(keyspecs_b)
-        kb = (_KeySpec * nk)()
-        kp = (_KeySpec * nk)()
-        for i, (sb, sp) in enumerate(zip(keyspecs_b, keyspecs_p)):
-            for arr, spec in ((kb, sb), (kp, sp)):
-                arr[i].col = spec[0]
-                arr[i].min = spec[1]
-                arr[i].range = spec[2]
-                arr[i].nullable = 1 if spec[3] else 0
-                arr[i].mode = spec[4] if len(spec) > 4 else 0
+        kb = self._keyspec_array(keyspecs_b)
+        kp = self._keyspec_array(keyspecs_p)
         n_out = len(out_specs)
         side_a = (ct.c_int32 * n_out)(*[s[0] for s in out_specs])
         col_a = (ct.c_int32 * n_out)(*[s[1] for s in out_specs])
@@ -704,13 +721,7 @@ class Runtime:
         bit2=NULLS LAST, passed in REVERSED significance order. Returns a
         DeviceColumn of u32 row ids or None (unsupported/skew → host)."""
         nk = len(keyspecs)
-        ks = (_KeySpec * nk)()
-        for i, spec in enumerate(keyspecs):
-            ks[i].col = spec[0]
-            ks[i].min = spec[1]
-            ks[i].range = spec[2]
-            ks[i].nullable = 1 if spec[3] else 0
-            ks[i].mode = spec[4]
+        ks = self._keyspec_array(keyspecs)
         perm = ct.c_void_p()
         rc = self.lib.dsx_sort_perm(self.ctx, self._cols_array(cols),
                                     ct.c_int(len(cols)), ks, ct.c_int(nk),
@@ -729,13 +740,7 @@ class Runtime:
         first it sorts composite keys of any width. Returns a DeviceColumn
         of u32 row ids or None (-3/-4: unsupported → host)."""
         nk = len(keyspecs)
-        ks = (_KeySpec * max(nk, 1))()
-        for i, spec in enumerate(keyspecs):
-            ks[i].col = spec[0]
-            ks[i].min = spec[1]
-            ks[i].range = spec[2]
-            ks[i].nullable = 1 if spec[3] else 0
-            ks[i].mode = spec[4]
+        ks = self._keyspec_array(keyspecs)
         if perm_in is not None and perm_in.len != n:
             raise DsxError(f"sort_word: perm_in has {perm_in.len} ids, "
                            f"expected {n}")
@@ -758,13 +763,7 @@ class Runtime:
         marks=None returns a new u8 DeviceColumn; a given one is ORed into
         and returned. None on -3/-4 (unsupported → host)."""
         nk = len(keyspecs)
-        ks = (_KeySpec * max(nk, 1))()
-        for i, spec in enumerate(keyspecs):
-            ks[i].col = spec[0]
-            ks[i].min = spec[1]
-            ks[i].range = spec[2]
-            ks[i].nullable = 1 if spec[3] else 0
-            ks[i].mode = spec[4]
+        ks = self._keyspec_array(keyspecs)
         for what, col in (("perm", perm), ("marks", marks)):
             if col is not None and col.len != n:
                 raise DsxError(f"window_mark_word: {what} has {col.len} "
@@ -865,13 +864,7 @@ class Runtime:
         self.lib.dsx_hash_table_free(table)
 
     def hash_groupby(self, cols, n, keyspecs, pred_prog, agg_specs):
-        # the C-side hist cache keys on device pointers with pool-free
-        # eviction; externally-backed key columns (torch/RCCL staging)
-        # recycle pointers outside that hook — disable for them
-        unsafe = any(
-            getattr(cols[spec[0]], "_keep_alive", None) is not None
-            and not getattr(cols[spec[0]], "_owner", True)
-            for spec in keyspecs)
+        unsafe = self._hist_cache_unsafe(cols, keyspecs)
         if unsafe:
             self.lib.dsx_gb_hist_cache_enable(self.ctx, 0)
         try:
@@ -885,20 +878,8 @@ class Runtime:
         """keyspecs: list of (col_idx, min, range, nullable) — key pack fused
         in-kernel. agg_specs: list of (agg_op, prog). Returns device pointers
         (out_codes, out_vals [naggs][G], out_counts [naggs][G], n_groups)."""
-        ks = (_KeySpec * max(len(keyspecs), 1))()
-        for i, spec in enumerate(keyspecs):
-            ci, mn, rng, nullable = spec[:4]
-            ks[i].mode = spec[4] if len(spec) > 4 else 0
-            ks[i].col = ci
-            ks[i].min = mn
-            ks[i].range = rng
-            ks[i].nullable = 1 if nullable else 0
-        aggs = (_AggSpec * max(len(agg_specs), 1))()
-        for i, (op, prog) in enumerate(agg_specs):
-            parr, plen = prog
-            aggs[i].op = op
-            aggs[i].prog_len = plen
-            ct.memmove(aggs[i].prog, parr, plen * ct.sizeof(_Instr))
+        ks = self._keyspec_array(keyspecs)
+        aggs = self._aggspec_array(agg_specs)
         if pred_prog is not None:
             pparr, pplen = pred_prog
         else:
@@ -930,24 +911,9 @@ class Runtime:
         n_groups); the columns own their buffers. Integer keys come back as
         I64 with a validity buffer only when nullable, a float (mode 1) key
         as F64 with one; COUNT as I64 without, every other call with."""
-        unsafe = any(
-            getattr(cols[spec[0]], "_keep_alive", None) is not None
-            and not getattr(cols[spec[0]], "_owner", True)
-            for spec in keyspecs)
-        ks = (_KeySpec * max(len(keyspecs), 1))()
-        for i, spec in enumerate(keyspecs):
-            ci, mn, rng, nullable = spec[:4]
-            ks[i].mode = spec[4] if len(spec) > 4 else 0
-            ks[i].col = ci
-            ks[i].min = mn
-            ks[i].range = rng
-            ks[i].nullable = 1 if nullable else 0
-        aggs = (_AggSpec * max(len(agg_specs), 1))()
-        for i, (op, prog) in enumerate(agg_specs):
-            parr, plen = prog
-            aggs[i].op = op
-            aggs[i].prog_len = plen
-            ct.memmove(aggs[i].prog, parr, plen * ct.sizeof(_Instr))
+        unsafe = self._hist_cache_unsafe(cols, keyspecs)
+        ks = self._keyspec_array(keyspecs)
+        aggs = self._aggspec_array(agg_specs)
         fc = (_GbFinishCall * max(len(calls), 1))()
         for i, (kind, agg) in enumerate(calls):
             fc[i].kind = self.GB_FIN_KINDS[kind]

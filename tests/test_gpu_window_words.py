@@ -469,3 +469,106 @@ def test_row_number_against_pandas(ctx, float_table):
     exp[s["rid"].to_numpy()] = rn.to_numpy()
     assert got["rn"].dtype == np.int64
     assert got["rn"].tolist() == exp.tolist()
+
+
+# ---- string ORDER BY key on the word route ---------------------------------
+RANKING = {"rn": "ROW_NUMBER() OVER ({w})", "rk": "RANK() OVER ({w})",
+           "dr": "DENSE_RANK() OVER ({w})"}
+
+
+@pytest.fixture(scope="module")
+def string_table(ctx):
+    """200 rows (more than one wave). s: six strings whose order of first
+    appearance (the dictionary's) is not alphabetical, some NULL; f: five
+    doubles with ties, some NaN; p: a small integer key."""
+    rng = np.random.default_rng(47)
+    n = 200
+    names = np.array(["pear", "apple", "quince", "fig", "banana", "cherry"],
+                     dtype=object)
+    s = names[rng.integers(0, 6, n)]
+    s[:6] = names                      # first appearance: this very order
+    s[rng.choice(np.arange(6, n), 15, replace=False)] = None
+    f = rng.choice(np.array([-3.5, -1.0, 0.25, 2.0, 1e9]), n)
+    f[rng.choice(n, 9, replace=False)] = np.nan
+    df = pd.DataFrame({"s": s, "f": f,
+                       "p": rng.integers(0, 4, n).astype(np.int64),
+                       "rid": np.arange(n, dtype=np.int64)})
+    ctx.create_table("ww_str", df)
+    return df
+
+
+def _ranking_expected(part, order):
+    """RANK, DENSE_RANK and the size of every row's peer class, by counting:
+    part / order hold one hashable partition key and one comparable order
+    key per row."""
+    n = len(part)
+    rk, dr, peers = [], [], []
+    for i in range(n):
+        mine = [order[j] for j in range(n) if part[j] == part[i]]
+        rk.append(1 + sum(o < order[i] for o in mine))
+        dr.append(1 + len({o for o in mine if o < order[i]}))
+        peers.append(sum(o == order[i] for o in mine))
+    return np.array(rk), np.array(dr), np.array(peers)
+
+
+def _check_ranking(got, part, order, what):
+    rk, dr, peers = _ranking_expected(part, order)
+    for c in RANKING:
+        assert got[c].dtype == np.int64, (what, c)
+    assert got["rk"].tolist() == rk.tolist(), what
+    assert got["dr"].tolist() == dr.tolist(), what
+    # ROW_NUMBER numbers the rows of a peer class rk .. rk+peers-1, in an
+    # order of its own choosing
+    rn = got["rn"].to_numpy()
+    assert ((rn >= rk) & (rn < rk + peers)).all(), what
+    assert len(set(zip(part, rn.tolist()))) == len(rn), what
+
+
+def _s_key(s):
+    return (s is None, s or "")       # alphabetical, NULL last
+
+
+def _f_key(f, desc=False):
+    nan = bool(np.isnan(f))           # NaN last in both directions
+    return (nan, 0.0 if nan else (-f if desc else f))
+
+
+def _assert_word_route(launches):
+    assert launches.get("k_rsort_scatter", 0) \
+        + launches.get("k_rsort_codes", 0) > 0, launches
+    assert launches.get("k_win_mark_word", 0) > 0, launches
+
+
+def test_string_order_key_on_the_word_route(ctx, string_table):
+    """The float key sends the window to the word front half, where the
+    string key sorts by its alphabetic rank — compared with the ranks
+    counted in Python, not with the host path (which reads a dictionary
+    order key's raw codes, in first-appearance order)."""
+    df = string_table
+    s, f, p = df["s"].tolist(), df["f"].tolist(), df["p"].tolist()
+    got, launches = _run(ctx, _sql("ww_str", "PARTITION BY p ORDER BY s, "
+                                             "f DESC", RANKING))
+    _assert_word_route(launches)
+    _check_ranking(got, p, [_s_key(a) + _f_key(b, desc=True)
+                            for a, b in zip(s, f)], "ORDER BY s, f DESC")
+    # a string PARTITION BY key goes by raw code, NULL a partition of its own
+    got, launches = _run(ctx, _sql("ww_str", "PARTITION BY s ORDER BY f",
+                                   RANKING))
+    _assert_word_route(launches)
+    _check_ranking(got, s, [_f_key(b) for b in f], "PARTITION BY s")
+
+
+def test_string_order_key_front_halves_agree(ctx, monkeypatch, string_table):
+    """ORDER BY s alone is all-integer: the bucket front half takes it by
+    default, DSX_WIN_WORDS=1 moves it to the word front half; same bits."""
+    df = string_table
+    sql = _sql("ww_str", "PARTITION BY p ORDER BY s", RANKING)
+    bucket, launches = _run(ctx, sql)
+    assert launches.get("k_win_mark_word", 0) == 0, launches
+    monkeypatch.setenv("DSX_WIN_WORDS", "1")
+    words, launches = _run(ctx, sql)
+    monkeypatch.delenv("DSX_WIN_WORDS")
+    _assert_word_route(launches)
+    _assert_identical(words, bucket, "word vs bucket front half")
+    _check_ranking(words, df["p"].tolist(),
+                   [_s_key(a) for a in df["s"].tolist()], "ORDER BY s")
