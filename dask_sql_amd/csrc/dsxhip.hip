@@ -76,6 +76,10 @@ struct DsxCtx {
   // memcpy→pinned + hipMemcpyAsync is the fast path
   void* pinned = nullptr;
   int64_t pinned_bytes = 0;
+  // pinned landing buffer of dsx_topk_rows (topk.inc): grows on demand, the
+  // returned host pointer stays valid until the next call on this context
+  void* topk_pinned = nullptr;
+  int64_t topk_pinned_bytes = 0;
   // balance-guard verdict cache for the direct-index groupby: keyed on the
   // key column's device pointer + shape — the distribution is a property
   // of the data, so the mid-pipeline totals sync runs once per table, not
@@ -211,6 +215,7 @@ extern "C" void dsx_ctx_destroy(DsxCtx* c) {
   }
   if (c->scratch) hipFree(c->scratch);
   if (c->pinned) hipHostFree(c->pinned);
+  if (c->topk_pinned) hipHostFree(c->topk_pinned);
   hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1439,7 +1444,9 @@ extern "C" int dsx_keypack(DsxCtx* c, const DsxColumn* cols, int ncols,
 struct DsxHashTable {
   uint64_t* keys = nullptr;   // EMPTY_KEY = empty; packed: (code<<32)|rowid
   uint32_t* vals = nullptr;   // build row id (unpacked layout only)
-  uint32_t* matched = nullptr;
+  uint32_t* matched = nullptr;  // per-slot marks of a mark_matched probe;
+                                // allocated and cleared on first such use
+                                // (hash_table_ensure_matched), else NULL
   int64_t slots = 0;
   int64_t n_build = 0;
   int packed = 0;             // codes < 2^32-1 → one 8-B entry per slot,
@@ -1558,7 +1565,6 @@ static int hash_build_impl(DsxCtx* c, const uint64_t* codes,
   }
   if (pool_alloc(c, slots * 8, (void**)&t->keys) ||
       (!t->packed && pool_alloc(c, slots * 4, (void**)&t->vals)) ||
-      pool_alloc(c, slots * 4, (void**)&t->matched) ||
       pool_alloc(c, 4, (void**)&t->dup) ||
       (t->filter_mode != DSX_JF_NONE &&
        pool_alloc(c, t->filter_bytes, (void**)&t->filter))) {
@@ -1566,7 +1572,6 @@ static int hash_build_impl(DsxCtx* c, const uint64_t* codes,
     FAIL(-2, "hash table alloc failed (%lld slots)", (long long)slots);
   }
   HIP_TRY(hipMemsetAsync(t->keys, 0xFF, slots * 8, c->stream));
-  HIP_TRY(hipMemsetAsync(t->matched, 0, slots * 4, c->stream));
   HIP_TRY(hipMemsetAsync(t->dup, 0, 4, c->stream));
   if (t->filter)
     HIP_TRY(hipMemsetAsync(t->filter, 0, t->filter_bytes, c->stream));
@@ -1623,6 +1628,20 @@ extern "C" void dsx_hash_table_free(DsxHashTable* t) {
     pool_release(t->ctx, t->filter);
   }
   delete t;
+}
+
+// Only a mark_matched probe writes the marks and only dsx_hash_unmatched
+// reads them, so a build does not pay for them: the first of the two
+// allocates the slots x 4 B and clears them (a pool buffer comes back dirty).
+static int hash_table_ensure_matched(DsxCtx* c, DsxHashTable* t) {
+  if (t->matched) return 0;
+  int rc = pool_alloc(c, t->slots * 4, (void**)&t->matched);
+  if (rc) {
+    t->matched = nullptr;
+    return rc;
+  }
+  HIP_TRY(hipMemsetAsync(t->matched, 0, t->slots * 4, c->stream));
+  return 0;
 }
 
 // PASS=0: per-block match counts (LDS reduce — a single global counter
@@ -1758,6 +1777,10 @@ extern "C" int dsx_hash_probe(DsxCtx* c, DsxHashTable* t, const uint64_t* codes,
   int grid = (int)min((int64_t)MAX_GRID, (n + BLOCK - 1) / BLOCK);
   int rc = ensure_scratch(c, (grid + 2) * 8 + n * 8 + 64);
   if (rc) return rc;
+  if (mark_matched) {
+    rc = hash_table_ensure_matched(c, t);
+    if (rc) return rc;
+  }
   int64_t* block_counts = (int64_t*)c->scratch;
   int64_t* d_total = block_counts + grid;
   uint32_t* cache_slot = (uint32_t*)(d_total + 2);
@@ -2400,6 +2423,9 @@ extern "C" int dsx_hash_unmatched(DsxCtx* c, DsxHashTable* t,
   *out_build_idx = nullptr;
   *out_count = 0;
   int rc = ensure_scratch(c, 8);
+  if (rc) return rc;
+  // a table no mark_matched probe has touched: all marks 0, every build row
+  rc = hash_table_ensure_matched(c, t);
   if (rc) return rc;
   unsigned long long* counter = (unsigned long long*)c->scratch;
   HIP_TRY(hipMemsetAsync(counter, 0, 8, c->stream));
@@ -3377,8 +3403,9 @@ static int groupby_partition_impl(
                          c->stream));
   HIP_TRY(hipMemcpyAsync(d_A, &A, sizeof(AggArg), hipMemcpyHostToDevice,
                          c->stream));
-  HIP_TRY(hipMemsetAsync(d_counter, 0, 8, c->stream));
-  HIP_TRY(hipMemsetAsync(d_ovf, 0, 4, c->stream));
+  // d_counter and d_ovf are adjacent 16-byte cells: one memset, and one
+  // copy back after the aggregate kernel
+  HIP_TRY(hipMemsetAsync(d_counter, 0, 32, c->stream));
 
   // staged-scatter tile size: largest multiple of 1024 whose LDS footprint
   // (s_off + counters + bucket tags + AoS stage) fits the CU's 160 KiB,
@@ -3628,11 +3655,13 @@ static int groupby_partition_impl(
                          d_tmp_codes, d_tmp_vals, d_tmp_gcnt, d_ovf);
     }
   }
-  int h_ovf = 0;
-  unsigned long long G = 0;
-  HIP_TRY(hipMemcpyAsync(&h_ovf, d_ovf, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(&G, d_counter, 8, hipMemcpyDeviceToHost, c->stream));
+  // the group count and the overflow flag sit 16 bytes apart: one copy
+  unsigned long long h_res[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h_res, d_counter, 24, hipMemcpyDeviceToHost,
+                         c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  unsigned long long G = h_res[0];
+  int h_ovf = (int)(uint32_t)h_res[2];
   if (h_ovf) {
     *fell_back = true;
     return 0;
@@ -4149,6 +4178,7 @@ void jit_cache_destroy(DsxCtx* c) {
 #include "window.inc"
 #include "window_rows.inc"
 #include "window_words.inc"
+#include "topk.inc"
 
 // ---------------------------------------------------------------------------
 // dsx_jit_expr_source — TEST INFRASTRUCTURE: emit the JIT expression

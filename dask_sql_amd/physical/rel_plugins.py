@@ -2453,7 +2453,12 @@ class DaskLimitPlugin(BaseRelPlugin):
 
 
 def _device_topk_impl(context, inp, below, keys, k):
-    """ORDER BY + LIMIT over a large result: device sampled-threshold
+    """ORDER BY + LIMIT over a large result. k <= 1024 over a frame of at
+    most 16 fixed-width columns: dsx_topk_rows selects the exact candidate
+    rows and returns them with their columns in one host wait
+    (_topk_select_device; DSX_DISABLE_TOPK=1, read per call, turns it
+    off). Everything else, and what that call declines: device
+    sampled-threshold
     selection — a strided device sample picks an approximate k-th key,
     a device filter keeps only rows at or beyond it, and the (tiny)
     candidate set is sorted exactly on host with full tie-breaking.
@@ -2472,6 +2477,13 @@ def _device_topk_impl(context, inp, below, keys, k):
     if col0.dtype not in (rt.F64, rt.I64, rt.I32, rt.I8):
         return None  # unsupported key dtype: host fallback
     isf = col0.dtype == rt.F64
+    # exact selection in one native call; whatever it declines (see
+    # _topk_select_device) takes the sampled-threshold path below unchanged
+    picked = _topk_select_device(runtime, inp, keys, k, n)
+    if picked is not None:
+        pdf = _topk_raw_frame(*picked, cc.columns, below, keys, k)
+        if pdf is not None:
+            return pdf
     # NULL/NaN keys are folded into the candidate filter below (they all
     # pass it and surface on host); no separate full scan + sync needed
     # strided device sample → approximate k-th order statistic. The index
@@ -2538,55 +2550,99 @@ def _device_topk_impl(context, inp, below, keys, k):
         raws.append(arr)
         valids.append(valid)
         srcs.append(col)
-    for i, _a, _nf in keys:
-        if getattr(srcs[i], "dictionary", None) is not None:
-            break  # dict key: code order != string order → converted path
-        if valids[i] is not None and not valids[i].all():
-            break
-        if np.asarray(raws[i]).dtype.kind == "f" and                 np.isnan(raws[i]).any():
-            break
-    else:
-        import pandas as pd
-
-        # np.lexsort: last key = primary; DESC via exact negation (f64 and
-        # sub-64-bit ints negate exactly in i64/f64; i64 at INT64_MIN bails)
-        lex = []
-        ok = True
-        for i, a, _nf in keys:
-            arr = np.asarray(raws[i])
-            if a:
-                lex.append(arr)
-            elif arr.dtype.kind == "f":
-                lex.append(-arr)
-            else:
-                a64 = arr.astype(np.int64)
-                if a64.size and a64.min() == np.iinfo(np.int64).min:
-                    ok = False
-                    break
-                lex.append(-a64)
-        if ok:
-            top = np.lexsort(tuple(reversed(lex)))[:k]
-        else:
-            raw_pdf = pd.DataFrame({j: raws[j] for j in range(len(raws))})
-            by = [i for i, _a, _nf in keys]
-            asc = [a for _i, a, _nf in keys]
-            top = raw_pdf.sort_values(by, ascending=asc,
-                                      kind="stable").index[:k].to_numpy()
-        from dask_sql_amd.materialize import _convert
-        fields = below.getRowType().getFieldList()
-        data = {}
-        for j, frontend in enumerate(ccc.columns):
-            sql_t = fields[j].getType().getSqlType() if j < len(fields)                 else None
-            v = valids[j][top] if valids[j] is not None else None
-            data[frontend] = _convert(raws[j][top], v, srcs[j],
-                                      sql_t).reset_index(drop=True)
-        return pd.DataFrame(data)
+    pdf = _topk_raw_frame(raws, valids, srcs, ccc.columns, below, keys, k)
+    if pdf is not None:
+        return pdf
     from dask_sql_amd.materialize import to_pandas
     pdf = to_pandas(cand_dc, context, below.getRowType())
     kcol = pdf.iloc[:, idx0]
     if kcol.isna().to_numpy().any():
         return None  # NULL/NaN keys present: exact NULLS ordering on host
     return _topk(pdf, keys, k)
+
+
+def _topk_select_device(runtime, inp, keys, k, n):
+    """The candidate rows through dsx_topk_rows (one host wait): exactly the
+    rows whose primary key sorts at or before the k-th row's, in row order —
+    the order the threshold filter of _device_topk_impl emits its candidates
+    in, so ties break the same way. Returns (raws, valids, srcs) or None
+    when the shape is not routed there (k > 1024, more than 16 columns, a
+    dtype the call does not carry, a dictionary ORDER BY key,
+    DSX_DISABLE_TOPK=1) or the call answers "not applicable"."""
+    import os as _os
+    if k > 1024 or _os.environ.get("DSX_DISABLE_TOPK", "0") == "1":
+        return None
+    cc = inp.column_container
+    srcs = [inp.table.col(cc.get_backend_by_frontend_name(f))
+            for f in cc.columns]
+    if len(srcs) > rt.MAX_COLS or any(
+            s.dtype not in (rt.I8, rt.I32, rt.I64, rt.F32, rt.F64)
+            for s in srcs):
+        return None
+    if any(getattr(srcs[i], "dictionary", None) is not None
+           for i, _a, _nf in keys):
+        return None
+    idx0, asc0, _ = keys[0]
+    res = runtime.topk_rows(srcs, idx0, not asc0, n, k,
+                            min(4096, max(4 * k, 1024)))
+    if res is None:
+        return None
+    rowids, cols = res
+    order = np.argsort(rowids, kind="stable")
+    raws = [vals[order] for vals, _v in cols]
+    valids = [v[order] if v is not None else None for _vals, v in cols]
+    return raws, valids, srcs
+
+
+def _topk_raw_frame(raws, valids, srcs, fronts, below, keys, k):
+    """Top k of the candidate rows, ordered on their RAW columns (day-ints,
+    codes), converting only the k winners. Returns None when raw order is
+    not the converted order or NULLS placement matters: a dictionary key, a
+    NULL or a NaN in a key column."""
+    for i, _a, _nf in keys:
+        if getattr(srcs[i], "dictionary", None) is not None:
+            return None  # dict key: code order != string order
+        if valids[i] is not None and not valids[i].all():
+            return None
+        if np.asarray(raws[i]).dtype.kind == "f" and \
+                np.isnan(raws[i]).any():
+            return None
+    import pandas as pd
+
+    # np.lexsort: last key = primary; DESC via exact negation (f64 and
+    # sub-64-bit ints negate exactly in i64/f64; i64 at INT64_MIN bails)
+    lex = []
+    ok = True
+    for i, a, _nf in keys:
+        arr = np.asarray(raws[i])
+        if a:
+            lex.append(arr)
+        elif arr.dtype.kind == "f":
+            lex.append(-arr)
+        else:
+            a64 = arr.astype(np.int64)
+            if a64.size and a64.min() == np.iinfo(np.int64).min:
+                ok = False
+                break
+            lex.append(-a64)
+    if ok:
+        top = np.lexsort(tuple(reversed(lex)))[:k]
+    else:
+        raw_pdf = pd.DataFrame({j: raws[j] for j in range(len(raws))})
+        by = [i for i, _a, _nf in keys]
+        asc = [a for _i, a, _nf in keys]
+        top = raw_pdf.sort_values(by, ascending=asc,
+                                  kind="stable").index[:k].to_numpy()
+    from dask_sql_amd.materialize import _convert
+    fields = below.getRowType().getFieldList()
+    data = {}
+    for j, frontend in enumerate(fronts):
+        sql_t = fields[j].getType().getSqlType() if j < len(fields) \
+            else None
+        v = valids[j][top] if valids[j] is not None else None
+        data[frontend] = _convert(raws[j][top], v, srcs[j],
+                                  sql_t).reset_index(drop=True)
+    return pd.DataFrame(data)
 
 
 def _topk(pdf, keys, k):

@@ -590,6 +590,43 @@ class Runtime:
         )
         return b.value, count.value
 
+    def topk_rows(self, cols, key_idx, desc, n, k, cap):
+        """Candidate rows of ORDER BY ... LIMIT k (dsx_topk_rows): the rows
+        whose primary key cols[key_idx] sorts at or before the k-th row's,
+        selected on the device and fetched with one wait. Returns
+        (row_ids u32[count], [(values, valid-bool-or-None) per column]) as
+        host arrays in no particular order, or None when the call is not
+        applicable (NULL / NaN primary key, ties past `cap`)."""
+        nc = len(cols)
+        host = ct.c_void_p()
+        offs = (ct.c_int64 * (1 + 2 * nc))()
+        count = ct.c_int64()
+        rc = self.lib.dsx_topk_rows(
+            self.ctx, self._cols_array(cols), ct.c_int(nc),
+            ct.c_int(key_idx), ct.c_int(1 if desc else 0), ct.c_int64(n),
+            ct.c_int64(k), ct.c_int64(cap), ct.byref(host), offs,
+            ct.byref(count))
+        if rc == NOT_APPLICABLE:
+            return None
+        _check(self.lib, rc, "dsx_topk_rows")
+        cnt = count.value
+
+        def view(off, np_dtype):
+            # copy out of the context's pinned buffer: the next call reuses it
+            buf = (ct.c_char * (cnt * np_dtype.itemsize)).from_address(
+                host.value + off)
+            return np.frombuffer(buf, dtype=np_dtype, count=cnt).copy()
+
+        rowids = view(offs[0], np.dtype("uint32"))
+        out = []
+        for i, c in enumerate(cols):
+            vals = view(offs[1 + 2 * i], _DSX_TO_NP[c.dtype])
+            voff = offs[2 + 2 * i]
+            valid = view(voff, np.dtype("uint8")).astype(bool) \
+                if voff >= 0 else None
+            out.append((vals, valid))
+        return rowids, out
+
     def filter_cols(self, prog, cols, n, mats):
         """Fused filter + materialization (dsx_filter_cols): returns
         ([DeviceColumn per mat], n_out)."""

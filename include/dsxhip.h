@@ -245,7 +245,10 @@ enum DsxJoinType {  /* reference join.py:41-48 JOIN_TYPE_MAPPING */
  * Unordered (normalize by sort for comparisons); FULL OUTER is composed by
  * the host from LEFT + unmatched-build sweep (dsx_hash_unmatched). */
 /* mark_matched: record matched build slots (needed only when
- * dsx_hash_unmatched will run, i.e. FULL OUTER). */
+ * dsx_hash_unmatched will run, i.e. FULL OUTER). The marks (slots x 4 B) are
+ * allocated and cleared by the first mark_matched probe or
+ * dsx_hash_unmatched on the table, not by the build; dsx_hash_unmatched on a
+ * table never probed that way reports every build row. */
 int dsx_hash_probe(DsxCtx* ctx, DsxHashTable* t, const uint64_t* codes,
                    const uint8_t* validity, int64_t n, int join_type,
                    int mark_matched,
@@ -355,6 +358,34 @@ int dsx_sort_word(DsxCtx* ctx, const DsxColumn* cols, int ncols,
                   const DsxKeySpec* keys, int nkeys, int64_t n,
                   const uint32_t* perm_in /* nullable = identity */,
                   uint32_t** out_perm);
+
+/* Candidate rows of ORDER BY ... LIMIT k, selected on the device and brought
+ * to the host with one wait (reference physical/utils/sort.py:9-34 topk_sort:
+ * nsmallest / nlargest on the first key, then the full sort of what is left).
+ * cols: 1..DSX_MAX_COLS fixed-width columns (I8/I32/I64/F32/F64, with or
+ * without validity) of n rows; cols[key_col] is the PRIMARY sort key (I8/I32/
+ * I64/F64), desc its direction. The candidates are exactly the rows whose
+ * primary key sorts at or before the k-th row's primary key — the k-th order
+ * statistic with all its ties (-0.0 ties with +0.0) — in no particular order.
+ * An MSB-first radix select over the key's order code (csrc/topk_select.h)
+ * finds them; every launch is queued without a host wait, and ONE D2H copy
+ * into a pinned buffer owned by the context plus one stream synchronize
+ * return the result:
+ *   *out_host: the buffer, valid until the next dsx_topk_rows on ctx;
+ *   out_offsets[1 + 2*ncols] (caller array), byte offsets into it:
+ *     [0] row ids u32[count]; [1+2i] column i's values (its dtype)[count];
+ *     [2+2i] column i's validity bytes u8[count], -1 when cols[i] has none;
+ *   *out_count: k <= count <= cap.
+ * Returns DSX_NOT_APPLICABLE (nothing to read) when the primary key holds a
+ * NULL or a NaN, or when the candidates do not fit `cap` (ties across the
+ * k-th position): the caller orders such frames another way. -3 on a
+ * malformed call (n or k out of range, n > 0xFFFFFFFE, dtype). At most
+ * 2 * DSX_TOPK_PASSES + 1 kernel launches and one memset; device work space
+ * is the context's scratch arena. */
+int dsx_topk_rows(DsxCtx* ctx, const DsxColumn* cols, int ncols, int key_col,
+                  int desc, int64_t n, int64_t k, int64_t cap,
+                  const void** out_host, int64_t* out_offsets,
+                  int64_t* out_count);
 
 /* Device ordered window frames (reference rel/logical/window.py:212-428):
  * caller provides the sort permutation over (partition, order) keys and the
