@@ -70,6 +70,7 @@ struct DsxCtx {
   bool debug = false;
   void* jit_cache = nullptr;  // JitCacheMap (jit.inc)
   int64_t fprobe_jit_launches = 0;  // generated j_fprobe_mask launches
+  int64_t fprobe_agg_jit_launches = 0;  // generated j_fprobe_agg launches
   int64_t join_filter_builds[3] = {0, 0, 0};  // filtered builds per mode
   // pinned staging arena for host→HBM ingest (parquet path): pageable
   // hipMemcpy forces an internal staging copy at ~⅓ the PCIe rate;
@@ -2199,20 +2200,9 @@ __global__ void k_fprobe_mask(ProgArg prog, KeyArg K, ColsArg C, int64_t n,
   if (threadIdx.x == 0) block_counts[blockIdx.x] = s_count;
 }
 
-// position of the k-th (0-based) set bit of m; k < popcount(m)
-__device__ __forceinline__ int fp_select_bit(uint64_t m, int k) {
-  int pos = 0;
-#pragma unroll
-  for (int w = 32; w > 0; w >>= 1) {
-    int cnt = __popcll(m & ((1ull << w) - 1));
-    if (k >= cnt) {
-      k -= cnt;
-      m >>= w;
-      pos += w;
-    }
-  }
-  return pos;
-}
+// fp_select_bit, fp_wave_inclusive, fp_batch_row: the set bits of a batch of
+// mask words handed to the lanes of a wave
+#include "fprobe_lanes.h"
 
 // pass 2: each wave takes a CONTIGUOUS quarter of the block's mask words.
 // Up front the waves count their quarters and exchange the four totals
@@ -2226,7 +2216,7 @@ __global__ void k_fprobe_emit(KeyArg K, ColsArg C, int64_t n,
                               int64_t tmask, int packed, const uint64_t* mask,
                               const int64_t* block_offsets,
                               const JoinMatArg* Mp, int64_t total,
-                              unsigned int* dbg) {
+                              int need_bid, unsigned int* dbg) {
   __shared__ JoinMatArg s_M;  // LDS copy (see k_hash_probe_mat note)
   __shared__ int64_t s_tot[WAVES_PER_BLOCK];
   int64_t lo, hi;
@@ -2248,32 +2238,20 @@ __global__ void k_fprobe_emit(KeyArg K, ColsArg C, int64_t n,
   for (int64_t wb = c0; wb < c1; wb += 64) {
     uint64_t m = (wb + lane < c1) ? mask[wb + lane] : 0;
     int cnt = __popcll(m);
-    int inc = cnt;  // inclusive prefix of the batch's word counts
-    for (int d = 1; d < 64; d <<= 1) {
-      int t = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += t;
-    }
-    int exc = inc - cnt;
+    int inc = fp_wave_inclusive(cnt);  // of the batch's word counts
     int T = __shfl(inc, 63, 64);
-    uint32_t m_lo = (uint32_t)m, m_hi = (uint32_t)(m >> 32);
     for (int j0 = 0; j0 < T; j0 += 64) {
-      // all lanes search (shuffles stay outside divergent code); lanes past
-      // the batch total search for its last row and then sit out
+      // lanes past the batch total search for its last row and then sit out
       int j = min(j0 + lane, T - 1);
-      int L = 0;  // smallest lane whose inclusive count exceeds j
-      for (int step = 32; step > 0; step >>= 1) {
-        int v = __shfl(inc, L + step - 1, 64);
-        if (v <= j) L += step;
-      }
-      uint64_t mL = ((uint64_t)(uint32_t)__shfl((int)m_hi, L, 64) << 32) |
-                    (uint32_t)__shfl((int)m_lo, L, 64);
-      int k = j - __shfl(exc, L, 64);
+      int64_t r = fp_batch_row(m, inc, cnt, wb, j);
       if (j0 + lane < T) {
-        int64_t r = (wb + L) * 64 + fp_select_bit(mL, k);
         int64_t o = base + j;
         uint32_t bid = DSX_NULL_IDX;
-        bool hit = r < n && fp_probe(tkeys, tvals, tmask, packed,
-                                     pack_key(K, C, r), bid);
+        // a call that materializes no build-side column needs no build row
+        // id: the mask bit already says that the row matched
+        bool hit = r < n && (!need_bid ||
+                             fp_probe(tkeys, tvals, tmask, packed,
+                                      pack_key(K, C, r), bid));
         if (!hit || o >= total) atomicOr(dbg, 2u);
         else jm_write(M, o, r, bid);
       }
@@ -2295,6 +2273,32 @@ static void fprobe_mask_jit_launch(DsxCtx* c, hipFunction_t f, int grid,
 
 extern "C" int64_t dsx_fprobe_jit_launches(DsxCtx* c) {
   return c->fprobe_jit_launches;
+}
+
+// the mask pass of dsx_filter_probe_cols and dsx_filter_probe_groupby:
+// generated kernel first; the interpreter is the fallback (JIT off,
+// DSX_DISABLE_JIT_FPROBE=1, predicate rejected, hipRTC failure).
+// DSX_DISABLE_JOINFILTER=1 (read per call) also ignores a filter the table
+// already has. extra[0] receives the table's dup flag.
+static void fprobe_mask_pass(DsxCtx* c, DsxHashTable* t, const DsxInstr* prog,
+                             int prog_len, const ProgArg& P, const KeyArg& K,
+                             const ColsArg& C, int64_t n, int grid,
+                             uint64_t* mask, int64_t* block_counts,
+                             int64_t* extra) {
+  int jf_mode = join_filter_enabled() ? t->filter_mode : DSX_JF_NONE;
+  hipFunction_t fj = fprobe_mask_jit_fn(c, P, K, C, t->packed, jf_mode);
+  ProfScope ps(c, "k_fprobe_mask");
+  if (fj) {
+    fprobe_mask_jit_launch(c, fj, grid, C, n, t->keys, t->slots - 1, t->dup,
+                           mask, block_counts, extra, t->filter,
+                           t->filter_arg);
+  } else {
+    auto kern = vm_prog_is_lite(prog, prog_len) ? k_fprobe_mask<true>
+                                                : k_fprobe_mask<false>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, c->stream, P, K, C, n,
+                       t->keys, t->vals, t->slots - 1, t->packed, t->dup, mask,
+                       block_counts, extra, t->filter, jf_mode, t->filter_arg);
+  }
 }
 
 extern "C" int dsx_filter_probe_cols(
@@ -2336,27 +2340,8 @@ extern "C" int dsx_filter_probe_cols(
       (JoinMatArg*)((char*)c->scratch + ((arg_off + 63) / 64) * 64);
   int64_t h_res[2] = {0, 0};
   if (grid > 0) {
-    {
-      // generated kernel first; the interpreter is the fallback (JIT off,
-      // DSX_DISABLE_JIT_FPROBE=1, predicate rejected, hipRTC failure)
-      // DSX_DISABLE_JOINFILTER=1 (read per call) also ignores a filter the
-      // table already has
-      int jf_mode = join_filter_enabled() ? t->filter_mode : DSX_JF_NONE;
-      hipFunction_t fj = fprobe_mask_jit_fn(c, P, K, C, t->packed, jf_mode);
-      ProfScope ps(c, "k_fprobe_mask");
-      if (fj) {
-        fprobe_mask_jit_launch(c, fj, grid, C, n, t->keys, t->slots - 1,
-                               t->dup, mask, block_counts, d_total + 1,
-                               t->filter, t->filter_arg);
-      } else {
-        auto kern = vm_prog_is_lite(prog, prog_len) ? k_fprobe_mask<true>
-                                                    : k_fprobe_mask<false>;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, c->stream, P, K,
-                           C, n, t->keys, t->vals, t->slots - 1, t->packed,
-                           t->dup, mask, block_counts, d_total + 1, t->filter,
-                           jf_mode, t->filter_arg);
-      }
-    }
+    fprobe_mask_pass(c, t, prog, prog_len, P, K, C, n, grid, mask,
+                     block_counts, d_total + 1);
     hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream,
                        block_counts, grid, d_total);
     HIP_TRY(hipMemcpyAsync(h_res, d_total, 16, hipMemcpyDeviceToHost,
@@ -2395,7 +2380,8 @@ extern "C" int dsx_filter_probe_cols(
     ProfScope ps(c, "k_fprobe_emit");
     hipLaunchKernelGGL(k_fprobe_emit, dim3(grid), dim3(BLOCK), 0, c->stream,
                        K, C, n, t->keys, t->vals, t->slots - 1, t->packed,
-                       mask, block_counts, d_M, total, c->dbg_flag);
+                       mask, block_counts, d_M, total, n_bcols > 0 ? 1 : 0,
+                       c->dbg_flag);
   }
   HIP_TRY(hipGetLastError());
   *out_count = total;
@@ -4007,6 +3993,9 @@ extern "C" int dsx_hash_groupby(DsxCtx* c, const DsxColumn* cols, int ncols,
                            out_groups, nullptr);
 }
 
+static int gb_finish_calls_check(const DsxAggSpec* aggs, int naggs,
+                                 const DsxGbFinishCall* calls, int ncalls);
+
 extern "C" int dsx_hash_groupby_cols(
     DsxCtx* c, const DsxColumn* cols, int ncols, int64_t n,
     const DsxKeySpec* keys, int nkeys, const DsxInstr* pred, int pred_len,
@@ -4015,6 +4004,19 @@ extern "C" int dsx_hash_groupby_cols(
   if (nkeys < 1 || nkeys > DSX_MAX_KEYS || naggs > DSX_MAX_AGGS ||
       ncalls < 0 || ncalls > DSX_MAX_AGGS)
     FAIL(-3, "groupby finish spec too large or without keys");
+  int rc = gb_finish_calls_check(aggs, naggs, calls, ncalls);
+  if (rc) return rc;
+  GbFinishReq R{calls, ncalls, out_datas, out_valids};
+  uint64_t* oc = nullptr;
+  void* ov = nullptr;
+  uint64_t* on = nullptr;
+  return hash_groupby_impl(c, cols, ncols, n, keys, nkeys, pred, pred_len,
+                           aggs, naggs, &oc, &ov, &on, out_groups, &R);
+}
+
+// every finish call names an accumulator whose op fits its kind
+static int gb_finish_calls_check(const DsxAggSpec* aggs, int naggs,
+                                 const DsxGbFinishCall* calls, int ncalls) {
   for (int i = 0; i < ncalls; i++) {
     int a = calls[i].agg;
     if (a < 0 || a >= naggs) FAIL(-3, "finish call names no accumulator");
@@ -4034,12 +4036,7 @@ extern "C" int dsx_hash_groupby_cols(
       FAIL(-3, "finish kind %d does not fit accumulator op %d",
            calls[i].kind, aggs[a].op);
   }
-  GbFinishReq R{calls, ncalls, out_datas, out_valids};
-  uint64_t* oc = nullptr;
-  void* ov = nullptr;
-  uint64_t* on = nullptr;
-  return hash_groupby_impl(c, cols, ncols, n, keys, nkeys, pred, pred_len,
-                           aggs, naggs, &oc, &ov, &on, out_groups, &R);
+  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -4179,6 +4176,7 @@ void jit_cache_destroy(DsxCtx* c) {
 #include "window_rows.inc"
 #include "window_words.inc"
 #include "topk.inc"
+#include "group_join.inc"
 
 // ---------------------------------------------------------------------------
 // dsx_jit_expr_source — TEST INFRASTRUCTURE: emit the JIT expression

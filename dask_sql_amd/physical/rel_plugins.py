@@ -469,23 +469,19 @@ class DaskJoinPlugin(BaseRelPlugin):
         "LEFTANTI": "leftanti", "CROSS": "cross",
     }
 
-    def convert(self, rel, context):
-        join = rel.join()
+    def convert(self, rel, context, inputs=None, table=None):
+        """inputs: the two converted input containers, when a caller (the
+        aggregate's group-join attempt) has converted them already; table:
+        the hash table that caller built over this join's build side with
+        the key filter (_fused_setup's sides), handed over for the fused
+        filter-probe join to use and free."""
         runtime = context._get_runtime()
-        dc_lhs, dc_rhs = self.assert_inputs(rel, 2, context)
-        cc_lhs = dc_lhs.column_container.make_unique("lhs")
-        cc_rhs = dc_rhs.column_container.make_unique("rhs")
-        dc_lhs = dc_lhs.with_columns(cc_lhs)
-        dc_rhs = dc_rhs.with_columns(cc_rhs)
-        n_lhs_cols = len(cc_lhs.columns)
-
-        join_type = self.JOIN_TYPE_MAPPING[str(join.getJoinType())]
-
-        condition = join.getCondition()
-        lhs_on, rhs_on, residual = [], [], []
-        if condition is not None:
-            lhs_on, rhs_on, residual = self._split_join_condition(
-                condition, n_lhs_cols)
+        J = self._prepare(rel, *(inputs if inputs is not None
+                                 else self.assert_inputs(rel, 2, context)))
+        join, dc_lhs, dc_rhs = J.join, J.dc_lhs, J.dc_rhs
+        cc_lhs, cc_rhs, n_lhs_cols = J.cc_lhs, J.cc_rhs, J.n_lhs_cols
+        join_type, residual = J.join_type, J.residual
+        lhs_on, rhs_on = J.lhs_on, J.rhs_on
 
         if (join_type == "leftanti" and getattr(join, "null_aware", False)
                 and rhs_on):
@@ -500,42 +496,20 @@ class DaskJoinPlugin(BaseRelPlugin):
                         return self._empty_output(rel, runtime, dc_lhs,
                                                   cc_lhs)
 
-        # materialize only columns the plan consumes (output_indices from the
-        # pruning pass) plus residual-referenced temporaries
         force_l = join_type in ("outer", "right")
         force_r = join_type in ("left", "outer")
-        combined = [("l", f) for f in cc_lhs.columns]
-        keep_rhs = join_type not in ("leftanti",)
-        if keep_rhs:
-            combined += [("r", f) for f in cc_rhs.columns]
-        out_idx = join.output_indices if getattr(join, "output_indices",
-                                                 None) is not None \
-            else list(range(len(combined)))
-        if (getattr(join, "output_indices", None) is None
-                and str(join.getJoinType()) == "LEFTSEMI"):
-            # unpruned SEMI join (e.g. below a UNION): lhs columns only
-            out_idx = list(range(n_lhs_cols))
+        combined, out_idx, mat_idx = J.combined, J.out_idx, J.mat_idx
+        null_eq = J.null_eq
         from dask_sql_amd.planner.prune import _expr_refs, _remap
 
         # FUSED PATH: emit writes the output columns directly — no pair
         # vectors, no per-column gathers (k_hash_probe_mat)
         import os as _os
         gathered = None
-        mat_idx = sorted(set(out_idx))
         # RADIX PATH first: once the flat probe table
         # outgrows the XCD L2, partition both sides and probe LDS-resident
         # bucket tables instead (dsx_radix_join)
-        null_eq = bool(getattr(join, "null_equal", False))
-        # FILTER-PROBE: a probe side that is a still-pending WHERE over a
-        # base table runs its predicate inside the probe sweep
-        # (dsx_filter_probe_cols); DSX_DISABLE_FILTERPROBE=1 restores the
-        # separate filter → keypack → probe passes
-        fprobe = None
-        if (join_type == "inner" and lhs_on and not residual and not null_eq
-                and len(mat_idx) <= 16
-                and not _os.environ.get("DSX_DISABLE_JOINFUSE")
-                and not _os.environ.get("DSX_DISABLE_FILTERPROBE")):
-            fprobe = self._filter_probe_side(dc_lhs, dc_rhs)
+        fprobe = self._fprobe_for(J)
         if (fprobe is None
                 and lhs_on and not residual and not null_eq
                 and len(mat_idx) <= 16
@@ -551,7 +525,11 @@ class DaskJoinPlugin(BaseRelPlugin):
                 and join_type in ("inner", "left", "right", "leftanti")):
             gathered, n_out = self._equi_join_fused(
                 runtime, dc_lhs, dc_rhs, lhs_on, rhs_on, join_type,
-                combined, mat_idx, cc_lhs, cc_rhs, fprobe=fprobe)
+                combined, mat_idx, cc_lhs, cc_rhs, fprobe=fprobe,
+                table=table)
+            table = None  # freed there
+        if table is not None:
+            runtime.hash_table_free(table)
 
         if gathered is None:
             if lhs_on:
@@ -636,6 +614,61 @@ class DaskJoinPlugin(BaseRelPlugin):
             mapping[name] = backend
         cc = ColumnContainer(field_names, mapping)
         return DataContainer(DeviceTable(out_cols, num_rows=n_out), cc)
+
+    def _prepare(self, rel, dc_lhs, dc_rhs):
+        """What the plan says about this join, over its two converted
+        inputs: unique column names, the join type, the split condition and
+        the columns to materialize."""
+        from types import SimpleNamespace
+        join = rel.join()
+        cc_lhs = dc_lhs.column_container.make_unique("lhs")
+        cc_rhs = dc_rhs.column_container.make_unique("rhs")
+        dc_lhs = dc_lhs.with_columns(cc_lhs)
+        dc_rhs = dc_rhs.with_columns(cc_rhs)
+        n_lhs_cols = len(cc_lhs.columns)
+
+        join_type = self.JOIN_TYPE_MAPPING[str(join.getJoinType())]
+
+        condition = join.getCondition()
+        lhs_on, rhs_on, residual = [], [], []
+        if condition is not None:
+            lhs_on, rhs_on, residual = self._split_join_condition(
+                condition, n_lhs_cols)
+
+        # materialize only columns the plan consumes (output_indices from the
+        # pruning pass) plus residual-referenced temporaries
+        combined = [("l", f) for f in cc_lhs.columns]
+        keep_rhs = join_type not in ("leftanti",)
+        if keep_rhs:
+            combined += [("r", f) for f in cc_rhs.columns]
+        out_idx = join.output_indices if getattr(join, "output_indices",
+                                                 None) is not None \
+            else list(range(len(combined)))
+        if (getattr(join, "output_indices", None) is None
+                and str(join.getJoinType()) == "LEFTSEMI"):
+            # unpruned SEMI join (e.g. below a UNION): lhs columns only
+            out_idx = list(range(n_lhs_cols))
+        return SimpleNamespace(
+            join=join, dc_lhs=dc_lhs, dc_rhs=dc_rhs, cc_lhs=cc_lhs,
+            cc_rhs=cc_rhs, n_lhs_cols=n_lhs_cols, join_type=join_type,
+            lhs_on=lhs_on, rhs_on=rhs_on, residual=residual,
+            combined=combined, out_idx=out_idx,
+            mat_idx=sorted(set(out_idx)),
+            null_eq=bool(getattr(join, "null_equal", False)))
+
+    def _fprobe_for(self, J):
+        """FILTER-PROBE: a probe side that is a still-pending WHERE over a
+        base table runs its predicate inside the probe sweep
+        (dsx_filter_probe_cols); DSX_DISABLE_FILTERPROBE=1 restores the
+        separate filter → keypack → probe passes. Returns the probe side
+        ("l"/"r") or None."""
+        import os as _os
+        if (J.join_type == "inner" and J.lhs_on and not J.residual
+                and not J.null_eq and len(J.mat_idx) <= 16
+                and not _os.environ.get("DSX_DISABLE_JOINFUSE")
+                and not _os.environ.get("DSX_DISABLE_FILTERPROBE")):
+            return self._filter_probe_side(J.dc_lhs, J.dc_rhs)
+        return None
 
     # -- helpers ------------------------------------------------------------
     def _empty_output(self, rel, runtime, dc_lhs, cc_lhs):
@@ -1072,20 +1105,14 @@ class DaskJoinPlugin(BaseRelPlugin):
             return "r" if pend_r else None
         return "l" if pend_l else None
 
-    def _equi_join_fused(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                         join_type, combined, mat_idx, cc_lhs, cc_rhs,
-                         fprobe=None):
-        """Equi join with fused emit+materialization (dsx_hash_probe_cols):
-        the probe's emit pass writes the output columns directly. Returns
-        ({combined_idx: DeviceColumn}, n_out) or (None, 0) on unsupported
-        shapes (caller falls back to the pair path).
-
-        fprobe "l"/"r": that side is a pending DeferredFilter and the probe
-        side of an INNER join — keys, ranges and sources then come from its
-        UNFILTERED base columns and the predicate runs inside the probe
-        (dsx_filter_probe_cols). The ranges are the base columns' cached
-        stats either way (_stats_src), so codes and table layout do not
-        change."""
+    def _fused_setup(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
+                     join_type, fprobe):
+        """Sides, key ranges and the fused entry's column list for
+        _equi_join_fused and the aggregate's group-join; None when a key is
+        not an integer kind. fp_cols / fp_keys (pending side only): the
+        probe-side program columns plus key columns in ONE list, and the
+        key specs indexing it; the caller checks the list's length."""
+        from types import SimpleNamespace
         pending = {"l": dc_lhs, "r": dc_rhs}.get(fprobe)
         if fprobe == "l":
             dc_lhs = dc_lhs.unfiltered()
@@ -1095,10 +1122,10 @@ class DaskJoinPlugin(BaseRelPlugin):
         rcols = dc_rhs.backend_cols()
         for i in lhs_on:
             if lcols[i].dtype not in _INT_KINDS:
-                return None, 0  # float keys: pair path densifies them
+                return None
         for i in rhs_on:
             if rcols[i].dtype not in _INT_KINDS:
-                return None, 0
+                return None
         kdc_rhs, krcols = self._reconcile_dict_keys(runtime, dc_lhs, dc_rhs,
                                                     lhs_on, rhs_on)
         ranges = []
@@ -1123,8 +1150,6 @@ class DaskJoinPlugin(BaseRelPlugin):
                 "leftanti": rt.JOIN_LEFTANTI,
             }[join_type]
 
-        # probe-side program columns + key columns in ONE list for the
-        # fused entry (16 at most, else filter first)
         fp_cols = fp_keys = None
         if pending is not None:
             fp_cols = list(pending.prog_cols)
@@ -1137,15 +1162,49 @@ class DaskJoinPlugin(BaseRelPlugin):
                     fp_cols.append(pk[pi])
                     ci = len(fp_cols) - 1
                 fp_keys.append((ci, mn, rng, False))
-            if len(fp_cols) > rt.MAX_COLS:
-                return self._equi_join_fused(
-                    runtime, *self._materialized(fprobe, pending, dc_lhs,
-                                                 dc_rhs),
-                    lhs_on, rhs_on, join_type, combined, mat_idx, cc_lhs,
-                    cc_rhs)
+        return SimpleNamespace(
+            pending=pending, dc_lhs=dc_lhs, dc_rhs=dc_rhs, swap=swap,
+            ranges=ranges, ktype=ktype, probe_kdc=probe_kdc,
+            build_kdc=build_kdc, probe_on=probe_on, build_on=build_on,
+            fp_cols=fp_cols, fp_keys=fp_keys)
 
-        bcodes, bval, bkeep, space = self._key_codes(
-            runtime, build_kdc, build_on, ranges)
+    def _equi_join_fused(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
+                         join_type, combined, mat_idx, cc_lhs, cc_rhs,
+                         fprobe=None, table=None):
+        """Equi join with fused emit+materialization (dsx_hash_probe_cols):
+        the probe's emit pass writes the output columns directly. Returns
+        ({combined_idx: DeviceColumn}, n_out) or (None, 0) on unsupported
+        shapes (caller falls back to the pair path).
+
+        fprobe "l"/"r": that side is a pending DeferredFilter and the probe
+        side of an INNER join — keys, ranges and sources then come from its
+        UNFILTERED base columns and the predicate runs inside the probe
+        (dsx_filter_probe_cols). The ranges are the base columns' cached
+        stats either way (_stats_src), so codes and table layout do not
+        change."""
+        S = self._fused_setup(runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
+                              join_type, fprobe)
+        pending = S.pending if S is not None else None
+        if table is not None and (pending is None
+                                  or len(S.fp_cols) > rt.MAX_COLS):
+            # cannot happen: the table's builder went through the same setup
+            runtime.hash_table_free(table)
+            table = None
+        if S is None:
+            return None, 0  # float keys: pair path densifies them
+        pending, dc_lhs, dc_rhs = S.pending, S.dc_lhs, S.dc_rhs
+        if S.fp_cols is not None and len(S.fp_cols) > rt.MAX_COLS:
+            # 16 program + key columns at most, else filter first
+            return self._equi_join_fused(
+                runtime, *self._materialized(fprobe, pending, dc_lhs,
+                                             dc_rhs),
+                lhs_on, rhs_on, join_type, combined, mat_idx, cc_lhs,
+                cc_rhs)
+        swap, ranges, ktype = S.swap, S.ranges, S.ktype
+        probe_kdc, build_kdc = S.probe_kdc, S.build_kdc
+        probe_on, build_on = S.probe_on, S.build_on
+        fp_cols, fp_keys = S.fp_cols, S.fp_keys
+
         # assemble per-side materialization lists (sources: ORIGINAL tables)
         probe_is_l = not swap
         p_items, b_items = [], []
@@ -1159,9 +1218,13 @@ class DaskJoinPlugin(BaseRelPlugin):
                     cc_rhs.get_backend_by_frontend_name(frontend))
             on_probe = (side == "l") == probe_is_l
             (p_items if on_probe else b_items).append((i, col))
-        # only the fused filter-probe reads the key-membership filter
-        table = runtime.hash_build(bcodes, bval, code_max=space - 1,
-                                   key_filter=pending is not None)
+        # only the fused filter-probe reads the key-membership filter; a
+        # table handed in (a declined group-join's) is that same build
+        if table is None:
+            bcodes, bval, bkeep, space = self._key_codes(
+                runtime, build_kdc, build_on, ranges)
+            table = runtime.hash_build(bcodes, bval, code_max=space - 1,
+                                       key_filter=pending is not None)
         try:
             res = None
             if pending is not None:
@@ -1583,8 +1646,20 @@ class DaskAggregatePlugin(BaseRelPlugin):
         for e in group_exprs:
             if not isinstance(named[e.getIndex()][0], InputRef):
                 return None
+        join_inputs = None
+        if base_rel.get_current_node_type() == "Join" and not pred_exprs:
+            out, join_inputs, join_table = self._try_group_join(
+                runtime, rel, agg, context, base_rel, named, group_exprs,
+                calls)
+            if out is not None:
+                return out
         try:
-            base_dc = RelConverter.convert(base_rel, context)
+            if join_inputs is not None:
+                # the attempt converted the join's inputs; they run once
+                base_dc = RelConverter._plugins["Join"].convert(
+                    base_rel, context, inputs=join_inputs, table=join_table)
+            else:
+                base_dc = RelConverter.convert(base_rel, context)
             base_cols = base_dc.backend_cols()
             dicts = _dicts_of(base_cols)
             group_meta = []
@@ -1628,6 +1703,172 @@ class DaskAggregatePlugin(BaseRelPlugin):
         return self._device_exec(runtime, rel, base_cols,
                                  base_dc.table.num_rows, keyspecs, group_meta,
                                  pred_prog, calls, specs, fins, slab)
+
+    def _finished_output(self, rel, group_meta, kcols, calls, acols,
+                         float_key=None):
+        """The aggregate's container from finished device columns: key
+        columns (hash_groupby_cols / filter_probe_groupby) named and typed
+        after group_meta's (name, source column), then one column per
+        call."""
+        out_cols = {}
+        order_names = []
+        float_key = float_key or [False] * len(kcols)
+        for fk, (name, src), col in zip(float_key, group_meta, kcols):
+            if not fk and getattr(src, "dictionary", None) is not None:
+                col.dictionary = src.dictionary
+            col.logical_dtype = src.dtype
+            out_cols[f"g__{name}"] = col
+            order_names.append((name, f"g__{name}"))
+        for call, col in zip(calls, acols):
+            name = call.toString()
+            out_cols[f"a__{name}"] = col
+            order_names.append((name, f"a__{name}"))
+        cc = ColumnContainer([n for n, _ in order_names],
+                             dict(order_names))
+        cc = self.fix_column_to_row_type(cc, rel.getRowType())
+        return DataContainer(DeviceTable(out_cols), cc)
+
+    def _try_group_join(self, runtime, rel, agg, context, base_rel, named,
+                        group_exprs, calls):
+        """Aggregate(Projection(Join)) as one group-join sweep
+        (physical/group_join.py, Runtime.filter_probe_groupby). Returns
+        (DataContainer or None, inputs, table): inputs are the join's
+        converted inputs once this attempt has converted them, and table the
+        hash table of an attempt that the entry declined, both for the
+        caller to hand to the join (which frees the table)."""
+        from dask_sql_amd.physical import group_join as gj
+        from dask_sql_amd.planner.plan import Literal as PLiteral
+        from dask_sql_amd.planner.plan import SqlType
+        from dask_sql_amd.planner.prune import _expr_refs, _remap
+
+        jp = RelConverter._plugins.get("Join")
+        if gj.disabled() or not isinstance(jp, DaskJoinPlugin):
+            return None, None, None
+        if str(base_rel.join().getJoinType()) != "INNER":
+            return None, None, None
+        inputs = jp.assert_inputs(base_rel, 2, context)
+        J = jp._prepare(base_rel, *inputs)
+        fprobe = jp._fprobe_for(J)
+        out_idx = J.out_idx
+
+        def side_cols(dc):
+            return (dc.unfiltered() if _pending_filter(dc)
+                    else dc).backend_cols()
+
+        def kd(col, side):
+            if getattr(col, "dictionary", None) is not None:
+                return ("dict", side)  # string keys: per-side codes
+            return col.dtype
+
+        lcols, rcols = side_cols(J.dc_lhs), side_cols(J.dc_rhs)
+        key_dtypes = [(kd(lcols[li], "l"), kd(rcols[ri], "r"))
+                      for li, ri in zip(J.lhs_on, J.rhs_on)]
+        group_cols = []
+        for e in group_exprs:
+            pe = named[e.getIndex()][0]
+            group_cols.append(out_idx[pe.getIndex()]
+                              if isinstance(pe, InputRef) else None)
+        facts, arg_exprs = [], []
+        for call in calls:
+            args = agg.getArgs(call)
+            expr, refs = None, None
+            if args:
+                if not isinstance(args[0], InputRef):
+                    return None, inputs, None
+                expr = named[args[0].getIndex()][0]
+                refs = set()
+                _expr_refs(expr, refs)
+            arg_exprs.append((expr, refs))
+            facts.append(gj.AggFact(
+                agg.getAggregationFuncName(call).lower(),
+                None if refs is None else frozenset(out_idx[i] for i in refs),
+                bool(call.isDistinctAgg()),
+                call.getFilterExpr() is not None))
+        v = gj.verdict(
+            join_type=J.join_type, residual=bool(J.residual),
+            null_equal=J.null_eq, probe_side=fprobe,
+            n_lhs_cols=J.n_lhs_cols, lhs_on=J.lhs_on, rhs_on=J.rhs_on,
+            key_dtypes=key_dtypes, group_cols=group_cols, aggs=facts,
+            max_aggs=rt.MAX_AGGS, max_keys=rt.MAX_KEYS)
+        if not v:
+            logger.debug("aggregate: no group-join (%s)", v.reason)
+            return None, inputs, None
+        pending = J.dc_lhs if fprobe == "l" else J.dc_rhs
+        if pending.max_rows < gj.min_rows():
+            return None, inputs, None
+        S = jp._fused_setup(runtime, J.dc_lhs, J.dc_rhs, J.lhs_on, J.rhs_on,
+                            "inner", fprobe)
+        if S is None:
+            return None, inputs, None
+
+        def src_col(ci):
+            side, frontend = J.combined[ci]
+            dc, cc = (S.dc_lhs, J.cc_lhs) if side == "l" \
+                else (S.dc_rhs, J.cc_rhs)
+            return dc.table.col(cc.get_backend_by_frontend_name(frontend))
+
+        # the aggregate arguments' probe columns join the predicate's and
+        # the keys' in the entry's one column list
+        fp_cols = list(S.fp_cols)
+
+        def fp_index(k):
+            col = src_col(out_idx[k])
+            ci = next((i for i, c in enumerate(fp_cols) if c is col), None)
+            if ci is None:
+                fp_cols.append(col)
+                ci = len(fp_cols) - 1
+            return ci
+
+        remapped = []
+        for expr, refs in arg_exprs:
+            if expr is None:
+                remapped.append(PLiteral(1, SqlType("BIGINT")))
+            else:
+                remapped.append(_remap(expr, {k: fp_index(k) for k in refs}))
+        if len(fp_cols) > rt.MAX_COLS:
+            return None, inputs, None
+        try:
+            dicts = _dicts_of(fp_cols)
+            specs, fins, slab = [], [], []
+            for fact, expr in zip(facts, remapped):
+                speclist, fin = self._agg_spec_expr(fact.func, expr, fp_cols,
+                                                    dicts)
+                slab.append(len(specs))
+                for op, prog in speclist:
+                    specs.append((op, runtime.make_prog(prog)))
+                fins.append(fin)
+        except RexCompileError:
+            return None, inputs, None
+        if not all(f in runtime.GB_FIN_KINDS for f in fins) \
+                or len(specs) > rt.MAX_AGGS:
+            return None, inputs, None
+        build_cols = (S.dc_lhs if S.swap else S.dc_rhs).backend_cols()
+        kcols, group_meta = [], []
+        for e, g, (kind, i) in zip(group_exprs, group_cols, v.key_sources):
+            # a probe-side join key comes out as its build-side twin
+            kcols.append(build_cols[S.build_on[i]] if kind == "key"
+                         else src_col(g))
+            group_meta.append((named[e.getIndex()][1], src_col(g)))
+        bcodes, bval, bkeep, space = jp._key_codes(
+            runtime, S.build_kdc, S.build_on, S.ranges)
+        table = runtime.hash_build(bcodes, bval, code_max=space - 1,
+                                   key_filter=True)
+        try:
+            res = runtime.filter_probe_groupby(
+                table, runtime.make_prog(S.pending.prog), fp_cols, S.fp_keys,
+                S.pending.max_rows, specs, list(zip(fins, slab)), kcols)
+        except BaseException:
+            runtime.hash_table_free(table)
+            raise
+        if res is None:
+            # duplicate build keys: join, then group, over the same table
+            return None, inputs, table
+        runtime.hash_table_free(table)
+        out_k, out_a, _ = res
+        logger.debug("aggregate: group-join over %s", fprobe)
+        return self._finished_output(
+            rel, group_meta, out_k, calls, out_a,
+            [c.dtype in (rt.F64, rt.F32) for c in kcols]), inputs, None
 
     @staticmethod
     def _keyspecs_for(runtime, cols, group_idx):
@@ -1759,23 +2000,9 @@ class DaskAggregatePlugin(BaseRelPlugin):
             kcols, acols, G = runtime.hash_groupby_cols(
                 cols, n_rows, keyspecs, pred_prog, specs,
                 list(zip(fins, slab)))
-            out_cols = {}
-            order_names = []
-            for ks, (name, src), col in zip(keyspecs, group_meta, kcols):
-                if not (len(ks) > 4 and ks[4] == 1) and \
-                        getattr(src, "dictionary", None) is not None:
-                    col.dictionary = src.dictionary
-                col.logical_dtype = src.dtype
-                out_cols[f"g__{name}"] = col
-                order_names.append((name, f"g__{name}"))
-            for call, col in zip(calls, acols):
-                name = call.toString()
-                out_cols[f"a__{name}"] = col
-                order_names.append((name, f"a__{name}"))
-            cc = ColumnContainer([n for n, _ in order_names],
-                                 dict(order_names))
-            cc = self.fix_column_to_row_type(cc, rel.getRowType())
-            return DataContainer(DeviceTable(out_cols), cc)
+            return self._finished_output(
+                rel, group_meta, kcols, calls, acols,
+                [len(ks) > 4 and ks[4] == 1 for ks in keyspecs])
         oc, ov, on, G = runtime.hash_groupby(cols, n_rows,
                                              keyspecs, pred_prog, specs)
 

@@ -36,6 +36,7 @@ _DSX_SIZE = {I64: 8, F64: 8, I32: 4, F32: 4, I8: 1, BOOL8: 1}
 MAX_PROG = 120
 MAX_COLS = 16
 MAX_AGGS = 16
+MAX_KEYS = 4
 
 # agg ops (include/dsxhip.h DsxAggOp)
 AGG_SUM_F64, AGG_SUM_I64, AGG_COUNT = 0, 1, 2
@@ -990,6 +991,56 @@ class Runtime:
             out.append(DeviceColumn(self, datas[i], valids[i] or None, G,
                                     dtype, owner=True))
         return out[:len(keyspecs)], out[len(keyspecs):], G
+
+    def filter_probe_groupby(self, table, prog, cols, keyspecs, n, agg_specs,
+                             calls, kcols):
+        """Group-join (dsx_filter_probe_groupby): filter_probe_cols' sweep
+        over the unfiltered probe columns `cols`, grouped by build row
+        instead of materialized. agg_specs and calls as for
+        hash_groupby_cols, the programs reading `cols`; kcols are the
+        build-side sources of the output key columns. Returns ([key
+        DeviceColumn], [call DeviceColumn], n_groups) typed as
+        hash_groupby_cols types them, rows in build row order, or None when
+        the entry declines (duplicate build keys, accumulators too large;
+        nothing was allocated)."""
+        parr, plen = prog
+        ks = self._keyspec_array(keyspecs)
+        aggs = self._aggspec_array(agg_specs)
+        fc = (_GbFinishCall * max(len(calls), 1))()
+        for i, (kind, agg) in enumerate(calls):
+            fc[i].kind = self.GB_FIN_KINDS[kind]
+            fc[i].agg = agg
+        nout = len(kcols) + len(calls)
+        datas = (ct.c_void_p * max(nout, 1))()
+        valids = (ct.c_void_p * max(nout, 1))()
+        og = ct.c_int64()
+        rc = self.lib.dsx_filter_probe_groupby(
+            self.ctx, table, parr, ct.c_int(plen), self._cols_array(cols),
+            ct.c_int(len(cols)), ks, ct.c_int(len(keyspecs)), ct.c_int64(n),
+            aggs, ct.c_int(len(agg_specs)), fc, ct.c_int(len(calls)),
+            self._cols_array(kcols), ct.c_int(len(kcols)), datas, valids,
+            ct.byref(og))
+        if rc == NOT_APPLICABLE:
+            return None
+        _check(self.lib, rc, "dsx_filter_probe_groupby")
+        G = og.value
+        out = []
+        for i in range(nout):
+            if i < len(kcols):
+                dtype = F64 if kcols[i].dtype in (F64, F32) else I64
+            else:
+                dtype = F64 if calls[i - len(kcols)][0] in (
+                    "sum_f", "min_f", "max_f", "avg") else I64
+            out.append(DeviceColumn(self, datas[i], valids[i] or None, G,
+                                    dtype, owner=True))
+        return out[:len(kcols)], out[len(kcols):], G
+
+    def fprobe_agg_jit_launches(self) -> int:
+        """Launches so far of the per-shape generated accumulate kernel of
+        filter_probe_groupby; a call that leaves the count unchanged ran the
+        interpreter kernel (as fprobe_jit_launches) or had no rows."""
+        self.lib.dsx_fprobe_agg_jit_launches.restype = ct.c_int64
+        return int(self.lib.dsx_fprobe_agg_jit_launches(self.ctx))
 
     def partition(self, codes: DeviceColumn, nbuckets, validity_ptr=None):
         """Returns (sel DeviceColumn-like ptr wrapped, offsets np.ndarray)."""

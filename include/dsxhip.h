@@ -559,6 +559,41 @@ int dsx_hash_groupby_cols(DsxCtx* ctx,
                           void** out_datas, uint8_t** out_valids,
                           int64_t* out_groups);
 
+/* Group-join: the inner PK-FK join of dsx_filter_probe_cols grouped by the
+ * build key (plus other columns of the build side), without materializing the
+ * join rows. Build keys are unique on this path, so a matched probe row's
+ * group is its build row: the sweep accumulates the aggregates per build row
+ * and the finish writes one output row per build row that matched, in
+ * ascending build row order (csrc/group_join.inc).
+ *  - t, prog, cols, keys, n: as for dsx_filter_probe_cols.
+ *  - aggs, calls: as for dsx_hash_groupby_cols; the aggregate programs read
+ *    `cols` (the probe side) at the matched probe row.
+ *  - kcols: 1..DSX_MAX_KEYS build-side columns (len = the table's build rows),
+ *    gathered at the build row as the output key columns. Integer kinds come
+ *    back as i64 and float kinds as f64, as dsx_hash_groupby_cols returns its
+ *    keys, with a validity buffer iff the source has one.
+ * out_datas/out_valids: n_kcols + ncalls slots (keys first), pool allocations
+ * sized for every build row; *out_groups rows of each are written. One host
+ * wait per call.
+ * Returns DSX_NOT_APPLICABLE, with nothing allocated, when the table holds a
+ * duplicate build key or the accumulators (build rows x 8..264 bytes) exceed
+ * 4 GiB — the caller then joins and groups separately. */
+int dsx_filter_probe_groupby(DsxCtx* ctx, DsxHashTable* t,
+                             const DsxInstr* prog, int prog_len,
+                             const DsxColumn* cols, int ncols,
+                             const DsxKeySpec* keys, int nkeys, int64_t n,
+                             const DsxAggSpec* aggs, int naggs,
+                             const DsxGbFinishCall* calls, int ncalls,
+                             const DsxColumn* kcols, int n_kcols,
+                             void** out_datas, uint8_t** out_valids,
+                             int64_t* out_groups);
+/* The accumulate pass of dsx_filter_probe_groupby runs a kernel generated per
+ * query shape (hipRTC; key pack, aggregate expressions and record layout
+ * inlined) and falls back to the interpreter kernel under DSX_DISABLE_JIT,
+ * DSX_DISABLE_JIT_FPROBE=1 (read per call), or a hipRTC failure. Launches of
+ * the generated kernel on ctx so far: */
+int64_t dsx_fprobe_agg_jit_launches(DsxCtx* ctx);
+
 /* ---- shuffle support --------------------------------------- */
 
 /* replaces dask's hash-repartition "tasks" shuffle split
@@ -612,6 +647,10 @@ int dsx_jit_compile_check(const char* src);
 /* TEST INFRASTRUCTURE: compile-check the generated filter-probe kernel for
  * representative shapes at every unroll factor; 0 on success. */
 int dsx_jit_fprobe_selftest(void);
+
+/* TEST INFRASTRUCTURE: compile-check the generated accumulate kernel of
+ * dsx_filter_probe_groupby for two shapes; needs no GPU; 0 on success. */
+int dsx_jit_fprobe_agg_selftest(void);
 
 #ifdef __cplusplus
 }
