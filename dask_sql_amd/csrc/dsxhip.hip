@@ -1386,6 +1386,20 @@ __device__ __forceinline__ uint64_t pack_key(const KeyArg& K, const ColsArg& C,
   return code;
 }
 
+// false when any key column of row r is NULL (dsx_filter_probe_cols,
+// dsx_hash_build_cols: such a row neither matches nor is inserted)
+__device__ __forceinline__ bool fp_key_valid(const KeyArg& K, const ColsArg& C,
+                                             int64_t r) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < DSX_MAX_KEYS; j++) {
+    if (j >= K.nkeys) break;
+    const uint8_t* v = C.validity[K.k[j].col];
+    if (v && !v[r]) ok = false;  // NULL key never matches (join.py:202-213)
+  }
+  return ok;
+}
+
 __global__ void k_keypack(KeyArg K, ColsArg C, int64_t n, uint64_t* out) {
   int64_t lo, hi;
   block_range(n, 1, lo, hi);
@@ -1452,7 +1466,8 @@ struct DsxHashTable {
   int64_t n_build = 0;
   int packed = 0;             // codes < 2^32-1 → one 8-B entry per slot,
                               // single random read per probe
-  unsigned int* dup = nullptr;  // device flag: any duplicate build key
+  unsigned int* dup = nullptr;  // device flag: any duplicate build key; its
+                                // own allocation only when there is no filter
   // key-membership filter (join_filter.h), consulted by the filter-probe mask
   // pass only: most probes of a selective join end on an EMPTY slot, and a
   // filter small enough to stay in L2 answers those without a table line
@@ -1463,28 +1478,58 @@ struct DsxHashTable {
   DsxCtx* ctx = nullptr;
 };
 
-__global__ void k_hash_build(const uint64_t* codes, const uint8_t* validity,
-                             int64_t n, uint64_t* tkeys, uint32_t* tvals,
-                             int64_t mask, int packed, unsigned int* dup,
-                             uint32_t* filter, int filter_mode,
-                             uint64_t filter_arg) {
-  int64_t lo, hi;
-  block_range(n, 1, lo, hi);
-  bool saw_dup = false;
-  for (int64_t r = lo + threadIdx.x; r < hi; r += BLOCK) {
-    if (validity && !validity[r]) continue;  // NULL-key drop (join.py:202-213)
-    uint64_t cde = codes[r];
-    if (filter_mode == DSX_JF_EXACT) {
-      // a code past code_max cannot come from a caller that keeps its own
-      // bound; it is left out of the bitmap rather than written past it, and
-      // the probe side treats such codes as misses
-      if (cde <= filter_arg)
-        atomicOr(&filter[dsx_jf_exact_word(cde)], dsx_jf_exact_bit(cde));
-    } else if (filter_mode == DSX_JF_HASHED) {
-      uint64_t h = dsx_jf_mix64(cde);
-      atomicOr(&filter[dsx_jf_hashed_word(h, filter_arg)],
-               dsx_jf_hashed_bits(h));
+// DSX_DISABLE_BUILD_RUNCOMBINE=1 (read per build): one filter atomic per row,
+// as before the run combine — for measuring the combine on its own
+static bool build_runcombine_enabled() {
+  const char* e = getenv("DSX_DISABLE_BUILD_RUNCOMBINE");
+  return !(e && *e && strcmp(e, "0") != 0);
+}
+
+// The build kernels' row step after the key code is known: the filter bit,
+// then the CAS claim. EVERY lane of the wave calls it (`live` false for a row
+// that is past the end, filtered out or has a NULL key), because the exact
+// filter's bits are combined across the wave first: neighbouring lanes whose
+// codes fall in the same filter word form a run, a segmented OR by shuffles
+// (6 steps) collects the run's bits in its first lane, and only that lane
+// issues the atomicOr. Sorted dense build keys then cost the two or three
+// atomics of the words a wave's 64 codes span instead of 64; unsorted keys
+// give runs of one and the atomics of before. Two separate runs of one word each issue their own OR, and a lane
+// may pick up same-word bits from past its run: both leave the bitmap as it
+// would be. Returns whether the row met an equal key in the table.
+template <bool COMBINE>
+__device__ __forceinline__ bool hb_insert_row(
+    bool live, uint64_t cde, int64_t r, uint64_t* tkeys, uint32_t* tvals,
+    int64_t mask, int packed, uint32_t* filter, int filter_mode,
+    uint64_t filter_arg) {
+  if (filter_mode == DSX_JF_EXACT) {
+    // a code past code_max cannot come from a caller that keeps its own
+    // bound; it is left out of the bitmap rather than written past it, and
+    // the probe side treats such codes as misses
+    bool in = live && cde <= filter_arg;
+    if (COMBINE) {
+      // exact mode implies a packed table: the word index fits 32 bits
+      uint32_t word = in ? (uint32_t)dsx_jf_exact_word(cde) : 0xFFFFFFFFu;
+      uint32_t bits = in ? dsx_jf_exact_bit(cde) : 0u;
+      int lane = threadIdx.x & 63;
+      uint32_t prev = __shfl_up(word, 1, 64);
+      bool head = lane == 0 || prev != word;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        uint32_t w2 = __shfl_down(word, d, 64);
+        uint32_t b2 = __shfl_down(bits, d, 64);
+        if (lane + d < 64 && w2 == word) bits |= b2;
+      }
+      if (in && head) atomicOr(&filter[word], bits);
+    } else if (in) {
+      atomicOr(&filter[dsx_jf_exact_word(cde)], dsx_jf_exact_bit(cde));
     }
+  } else if (filter_mode == DSX_JF_HASHED && live) {
+    uint64_t h = dsx_jf_mix64(cde);
+    atomicOr(&filter[dsx_jf_hashed_word(h, filter_arg)],
+             dsx_jf_hashed_bits(h));
+  }
+  bool saw_dup = false;
+  if (live) {
     uint64_t entry = packed ? ((cde << 32) | (uint64_t)(uint32_t)r) : cde;
     int64_t s = (int64_t)(mix64(cde) & mask);
     while (true) {
@@ -1501,6 +1546,59 @@ __global__ void k_hash_build(const uint64_t* codes, const uint8_t* validity,
       if ((packed ? (old >> 32) : old) == cde) saw_dup = true;
       s = (s + 1) & mask;
     }
+  }
+  return saw_dup;
+}
+
+// the row loop of both build kernels keeps whole waves together (the run
+// combine shuffles across the wave): a wave leaves when its FIRST lane's row
+// is past the block's range
+template <bool COMBINE>
+__global__ void k_hash_build(const uint64_t* codes, const uint8_t* validity,
+                             int64_t n, uint64_t* tkeys, uint32_t* tvals,
+                             int64_t mask, int packed, unsigned int* dup,
+                             uint32_t* filter, int filter_mode,
+                             uint64_t filter_arg) {
+  int64_t lo, hi;
+  block_range(n, 1, lo, hi);
+  bool saw_dup = false;
+  int lane = threadIdx.x & 63;
+  for (int64_t r = lo + threadIdx.x; r - lane < hi; r += BLOCK) {
+    // NULL-key drop (join.py:202-213)
+    bool live = r < hi && !(validity && !validity[r]);
+    uint64_t cde = live ? codes[r] : 0;
+    saw_dup |= hb_insert_row<COMBINE>(live, cde, r, tkeys, tvals, mask, packed,
+                                      filter, filter_mode, filter_arg);
+  }
+  if (saw_dup) atomicOr(dup, 1u);
+}
+
+// dsx_hash_build_cols: predicate → key validity → pack → insert, one sweep
+// over the source columns; the stored row id is the source row's index
+// launch bounds: the full interpreter (LITE false) needs more than the 128
+// registers a 1024-thread default leaves it, and would spill
+template <bool LITE, bool COMBINE>
+__global__ void __launch_bounds__(BLOCK) k_hash_build_cols(ProgArg prog, KeyArg K, ColsArg C, int64_t n,
+                                  uint64_t* tkeys, uint32_t* tvals,
+                                  int64_t mask, int packed, unsigned int* dup,
+                                  uint32_t* filter, int filter_mode,
+                                  uint64_t filter_arg) {
+  int64_t lo, hi;
+  block_range(n, 1, lo, hi);
+  bool saw_dup = false;
+  int lane = threadIdx.x & 63;
+  for (int64_t r = lo + threadIdx.x; r - lane < hi; r += BLOCK) {
+    bool live = r < hi;
+    if (live && prog.len > 0) {
+      Slot v;
+      bool valid = vm_eval<LITE>(prog.ins, prog.len, C, r, v);
+      live = valid && v.i != 0;  // NULL → False
+    }
+    // NULL-key drop (join.py:202-213); such a row's code is garbage
+    live = live && fp_key_valid(K, C, r);
+    uint64_t cde = live ? pack_key(K, C, r) : 0;
+    saw_dup |= hb_insert_row<COMBINE>(live, cde, r, tkeys, tvals, mask, packed,
+                                      filter, filter_mode, filter_arg);
   }
   if (saw_dup) atomicOr(dup, 1u);
 }
@@ -1541,10 +1639,11 @@ static void join_filter_plan(int64_t n, uint64_t code_max, int packed,
   *bytes = words * 4;
 }
 
-static int hash_build_impl(DsxCtx* c, const uint64_t* codes,
-                           const uint8_t* validity, int64_t n,
-                           uint64_t code_max, bool want_filter,
-                           DsxHashTable** out) {
+// an empty table for n build rows, cleared on the context's stream: slots from
+// n, layout from code_max, the filter from join_filter_plan. With a filter
+// the dup flag is the word after the filter's last, so one clear covers both.
+static int hash_table_new(DsxCtx* c, int64_t n, uint64_t code_max,
+                          bool want_filter, DsxHashTable** out) {
   if (n > 0xFFFFFFFEll) FAIL(-3, "build side too large for u32 row ids");
   static const double slots_mult = [] {
     const char* e = getenv("DSX_JOIN_SLOTS_MULT");
@@ -1564,25 +1663,90 @@ static int hash_build_impl(DsxCtx* c, const uint64_t* codes,
                      &t->filter_bytes);
     c->join_filter_builds[t->filter_mode]++;
   }
+  bool with_filter = t->filter_mode != DSX_JF_NONE;  // bytes: a multiple of 4
   if (pool_alloc(c, slots * 8, (void**)&t->keys) ||
       (!t->packed && pool_alloc(c, slots * 4, (void**)&t->vals)) ||
-      pool_alloc(c, 4, (void**)&t->dup) ||
-      (t->filter_mode != DSX_JF_NONE &&
-       pool_alloc(c, t->filter_bytes, (void**)&t->filter))) {
+      (with_filter ? pool_alloc(c, t->filter_bytes + 4, (void**)&t->filter)
+                   : pool_alloc(c, 4, (void**)&t->dup))) {
     dsx_hash_table_free(t);
     FAIL(-2, "hash table alloc failed (%lld slots)", (long long)slots);
   }
+  if (with_filter) t->dup = t->filter + t->filter_bytes / 4;
   HIP_TRY(hipMemsetAsync(t->keys, 0xFF, slots * 8, c->stream));
-  HIP_TRY(hipMemsetAsync(t->dup, 0, 4, c->stream));
-  if (t->filter)
-    HIP_TRY(hipMemsetAsync(t->filter, 0, t->filter_bytes, c->stream));
+  HIP_TRY(hipMemsetAsync(with_filter ? (void*)t->filter : (void*)t->dup, 0,
+                         with_filter ? t->filter_bytes + 4 : 4, c->stream));
+  *out = t;
+  return 0;
+}
+
+static int hash_build_impl(DsxCtx* c, const uint64_t* codes,
+                           const uint8_t* validity, int64_t n,
+                           uint64_t code_max, bool want_filter,
+                           DsxHashTable** out) {
+  DsxHashTable* t = nullptr;
+  int rc = hash_table_new(c, n, code_max, want_filter, &t);
+  if (rc) return rc;
   int grid = (int)min((int64_t)MAX_GRID, (n + BLOCK - 1) / BLOCK);
   if (grid > 0) {
     ProfScope ps(c, "k_hash_build");
-    hipLaunchKernelGGL(k_hash_build, dim3(grid), dim3(BLOCK), 0, c->stream,
-                       codes, validity, n, t->keys, t->vals, slots - 1,
-                       t->packed, t->dup, t->filter, t->filter_mode,
-                       t->filter_arg);
+    hipLaunchKernelGGL(build_runcombine_enabled() ? k_hash_build<true>
+                                                  : k_hash_build<false>,
+                       dim3(grid), dim3(BLOCK), 0, c->stream, codes, validity,
+                       n, t->keys, t->vals, t->slots - 1, t->packed, t->dup,
+                       t->filter, t->filter_mode, t->filter_arg);
+  }
+  HIP_TRY(hipGetLastError());
+  *out = t;
+  return 0;
+}
+
+// One sweep over source columns that builds the table dsx_hash_build_filtered
+// builds over the packed codes of the rows the predicate keeps: no compacted
+// columns, no code column, no combined-validity column, and no wait — the
+// slots come from n, since the survivor count is not known on the host.
+extern "C" int dsx_hash_build_cols(DsxCtx* c, const DsxInstr* prog,
+                                   int prog_len, const DsxColumn* cols,
+                                   int ncols, const DsxKeySpec* keys,
+                                   int nkeys, int64_t n, uint64_t code_max,
+                                   int key_filter, DsxHashTable** out) {
+  if (prog_len < 0 || prog_len > DSX_MAX_PROG || ncols > DSX_MAX_COLS ||
+      nkeys < 1 || nkeys > DSX_MAX_KEYS)
+    FAIL(-3, "build-from-columns spec too large");
+  ProgArg P{};
+  if (prog_len) memcpy(P.ins, prog, prog_len * sizeof(DsxInstr));
+  P.len = prog_len;
+  KeyArg K{};
+  int rc = make_keyarg(keys, nkeys, K);
+  if (rc) return rc;
+  for (int j = 0; j < nkeys; j++)
+    if (keys[j].mode != 0 || keys[j].col < 0 || keys[j].col >= ncols)
+      FAIL(-3, "build-from-columns takes radix-packed integer keys only");
+  for (int i = 0; i < prog_len; i++)
+    if (prog[i].op == DSX_OP_COL && (prog[i].arg0 < 0 || prog[i].arg0 >= ncols))
+      FAIL(-3, "predicate reads no source column");
+  ColsArg C{};
+  C.ncols = ncols;
+  for (int i = 0; i < ncols; i++) {
+    if (cols[i].len < n) FAIL(-3, "source column shorter than n");
+    C.data[i] = cols[i].data;
+    C.validity[i] = cols[i].validity;
+    C.dtype[i] = cols[i].dtype;
+  }
+  DsxHashTable* t = nullptr;
+  rc = hash_table_new(c, n, code_max, key_filter != 0, &t);
+  if (rc) return rc;
+  int grid = (int)min((int64_t)MAX_GRID, (n + BLOCK - 1) / BLOCK);
+  if (grid > 0) {
+    bool lite = vm_prog_is_lite(prog, prog_len);
+    bool comb = build_runcombine_enabled();
+    auto kern = lite ? (comb ? k_hash_build_cols<true, true>
+                             : k_hash_build_cols<true, false>)
+                     : (comb ? k_hash_build_cols<false, true>
+                             : k_hash_build_cols<false, false>);
+    ProfScope ps(c, "k_hash_build");
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, c->stream, P, K, C, n,
+                       t->keys, t->vals, t->slots - 1, t->packed, t->dup,
+                       t->filter, t->filter_mode, t->filter_arg);
   }
   HIP_TRY(hipGetLastError());
   *out = t;
@@ -1625,7 +1789,8 @@ extern "C" void dsx_hash_table_free(DsxHashTable* t) {
     pool_release(t->ctx, t->keys);
     pool_release(t->ctx, t->vals);
     pool_release(t->ctx, t->matched);
-    pool_release(t->ctx, t->dup);
+    // with a filter, dup is the filter allocation's last word
+    if (!t->filter) pool_release(t->ctx, t->dup);
     pool_release(t->ctx, t->filter);
   }
   delete t;
@@ -2113,18 +2278,6 @@ extern "C" int dsx_hash_probe_cols(
 // intermediates (compacted columns, code column, slot/count cache) with a
 // one-bit-per-row match mask.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ bool fp_key_valid(const KeyArg& K, const ColsArg& C,
-                                             int64_t r) {
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < DSX_MAX_KEYS; j++) {
-    if (j >= K.nkeys) break;
-    const uint8_t* v = C.validity[K.k[j].col];
-    if (v && !v[r]) ok = false;  // NULL key never matches (join.py:202-213)
-  }
-  return ok;
-}
-
 // first match of `cde` (build keys are unique on this path)
 __device__ __forceinline__ bool fp_probe(const uint64_t* tkeys,
                                          const uint32_t* tvals, int64_t mask,

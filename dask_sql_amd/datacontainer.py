@@ -116,7 +116,10 @@ class DeferredFilter(DataContainer):
     """A WHERE over a base table that has not run yet: the base container
     plus the compiled predicate. A join that probes with it fuses the
     predicate into the probe sweep (dsx_filter_probe_cols) and never builds
-    the filtered table; every other consumer reads `.table`, which runs the
+    the filtered table; an INNER join that builds its hash table from it
+    fuses the predicate into the build sweep (dsx_hash_build_cols), with row
+    ids that index the base columns (physical/filter_build.py says when);
+    every other consumer reads `.table`, which runs the
     ordinary fused filter (dsx_filter_cols) once and caches the result, so
     it sees exactly what an eager filter would have produced.
 

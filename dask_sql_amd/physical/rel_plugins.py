@@ -510,7 +510,10 @@ class DaskJoinPlugin(BaseRelPlugin):
         # outgrows the XCD L2, partition both sides and probe LDS-resident
         # bucket tables instead (dsx_radix_join)
         fprobe = self._fprobe_for(J)
-        if (fprobe is None
+        # a pending build side that the fused path builds straight from its
+        # base columns; the radix gate has declined such a join already
+        fbuild = self._fbuild_for(J, fprobe)
+        if (fprobe is None and fbuild is None
                 and lhs_on and not residual and not null_eq
                 and len(mat_idx) <= 16
                 and not _os.environ.get("DSX_DISABLE_RADIX")
@@ -526,7 +529,7 @@ class DaskJoinPlugin(BaseRelPlugin):
             gathered, n_out = self._equi_join_fused(
                 runtime, dc_lhs, dc_rhs, lhs_on, rhs_on, join_type,
                 combined, mat_idx, cc_lhs, cc_rhs, fprobe=fprobe,
-                table=table)
+                table=table, fbuild=fbuild)
             table = None  # freed there
         if table is not None:
             runtime.hash_table_free(table)
@@ -669,6 +672,43 @@ class DaskJoinPlugin(BaseRelPlugin):
                 and not _os.environ.get("DSX_DISABLE_FILTERPROBE")):
             return self._filter_probe_side(J.dc_lhs, J.dc_rhs)
         return None
+
+    @staticmethod
+    def _fb_verdict(join_type, fprobe, pend_l, pend_r, n_l, n_r,
+                    fusable=True, **setup_facts):
+        """physical/filter_build.verdict with the knobs read now."""
+        import os as _os
+
+        from dask_sql_amd.physical import filter_build as fb
+        radix = None if _os.environ.get("DSX_DISABLE_RADIX") else int(
+            _os.environ.get("DSX_RADIX_MIN_BUILD", 8_000_000))
+        return fb.verdict(
+            join_type=join_type, fusable=fusable, pend_l=pend_l,
+            pend_r=pend_r, n_l=n_l, n_r=n_r, probe_side=fprobe,
+            radix_min_build=radix, cap=fb.max_rows(), knob_off=fb.disabled(),
+            min_rows=fb.min_rows(),
+            max_cols=rt.MAX_COLS, **setup_facts)
+
+    def _fbuild_for(self, J, fprobe):
+        """FILTER-BUILD: the side ("l"/"r") whose still-pending WHERE runs
+        inside the hash build (dsx_hash_build_cols) because it is the build
+        side of a fused INNER join, or None (physical/filter_build.py)."""
+        import os as _os
+        pend_l, pend_r = _pending_filter(J.dc_lhs), _pending_filter(J.dc_rhs)
+        if not (pend_l or pend_r):
+            return None
+        fusable = bool(
+            J.lhs_on and not J.residual and not J.null_eq
+            and len(J.mat_idx) <= 16
+            and not _os.environ.get("DSX_DISABLE_JOINFUSE")
+            and J.join_type in ("inner", "left", "right", "leftanti"))
+        n_l = J.dc_lhs.max_rows if pend_l else J.dc_lhs.table.num_rows
+        n_r = J.dc_rhs.max_rows if pend_r else J.dc_rhs.table.num_rows
+        v = self._fb_verdict(J.join_type, fprobe, pend_l, pend_r, n_l, n_r,
+                             fusable=fusable)
+        if not v:
+            logger.debug("join: build side filters first (%s)", v.reason)
+        return v.side if v and v.pending else None
 
     # -- helpers ------------------------------------------------------------
     def _empty_output(self, rel, runtime, dc_lhs, cc_lhs):
@@ -1089,7 +1129,9 @@ class DaskJoinPlugin(BaseRelPlugin):
         fused in, or None. The probe side is the larger one; a pending
         filter's row count is not known before it runs, so it stands in with
         its base table's. A pending side that comes out as the build side
-        simply materializes. The radix path keeps priority: where both
+        stays pending too where _fbuild_for takes it (its WHERE then runs
+        inside the hash build, dsx_hash_build_cols) and materializes
+        otherwise. The radix path keeps priority: where both
         sides could pass its build-size gate the filters run first, as
         before, and the gate sees the real counts."""
         import os as _os
@@ -1106,17 +1148,21 @@ class DaskJoinPlugin(BaseRelPlugin):
         return "l" if pend_l else None
 
     def _fused_setup(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                     join_type, fprobe):
-        """Sides, key ranges and the fused entry's column list for
+                     join_type, fprobe, fbuild=None):
+        """Sides, key ranges and the fused entries' column lists for
         _equi_join_fused and the aggregate's group-join; None when a key is
-        not an integer kind. fp_cols / fp_keys (pending side only): the
+        not an integer kind. fp_cols / fp_keys (pending probe side only): the
         probe-side program columns plus key columns in ONE list, and the
-        key specs indexing it; the caller checks the list's length."""
+        key specs indexing it; the caller checks the list's length. fb_cols /
+        fb_keys: the same for the build side and dsx_hash_build_cols, with
+        the program columns of a pending build side (fbuild) or none;
+        key_rewritten says that the build key is a dictionary remap."""
         from types import SimpleNamespace
         pending = {"l": dc_lhs, "r": dc_rhs}.get(fprobe)
-        if fprobe == "l":
+        pending_b = {"l": dc_lhs, "r": dc_rhs}.get(fbuild)
+        if "l" in (fprobe, fbuild):
             dc_lhs = dc_lhs.unfiltered()
-        elif fprobe == "r":
+        if "r" in (fprobe, fbuild):
             dc_rhs = dc_rhs.unfiltered()
         lcols = dc_lhs.backend_cols()
         rcols = dc_rhs.backend_cols()
@@ -1134,6 +1180,8 @@ class DaskJoinPlugin(BaseRelPlugin):
 
         if fprobe is not None:
             swap = fprobe == "r"
+        elif fbuild is not None:
+            swap = fbuild == "l"
         else:
             swap = join_type == "right" or (
                 join_type == "inner"
@@ -1162,15 +1210,29 @@ class DaskJoinPlugin(BaseRelPlugin):
                     fp_cols.append(pk[pi])
                     ci = len(fp_cols) - 1
                 fp_keys.append((ci, mn, rng, False))
+        fb_cols = list(pending_b.prog_cols) if pending_b is not None else []
+        fb_keys = []
+        bk = build_kdc.backend_cols()
+        space = 1
+        for bi, (mn, rng) in zip(build_on, ranges):
+            ci = next((k for k, c in enumerate(fb_cols) if c is bk[bi]), None)
+            if ci is None:
+                fb_cols.append(bk[bi])
+                ci = len(fb_cols) - 1
+            fb_keys.append((ci, mn, rng, False))
+            space *= rng
         return SimpleNamespace(
             pending=pending, dc_lhs=dc_lhs, dc_rhs=dc_rhs, swap=swap,
             ranges=ranges, ktype=ktype, probe_kdc=probe_kdc,
             build_kdc=build_kdc, probe_on=probe_on, build_on=build_on,
-            fp_cols=fp_cols, fp_keys=fp_keys)
+            fp_cols=fp_cols, fp_keys=fp_keys, pending_b=pending_b,
+            fb_cols=fb_cols, fb_keys=fb_keys, fb_space=space,
+            key_rewritten=(not swap) and kdc_rhs is not dc_rhs)
 
     def _equi_join_fused(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
                          join_type, combined, mat_idx, cc_lhs, cc_rhs,
-                         fprobe=None, table=None):
+                         fprobe=None, table=None, fbuild=None,
+                         build_cols=True):
         """Equi join with fused emit+materialization (dsx_hash_probe_cols):
         the probe's emit pass writes the output columns directly. Returns
         ({combined_idx: DeviceColumn}, n_out) or (None, 0) on unsupported
@@ -1181,9 +1243,23 @@ class DaskJoinPlugin(BaseRelPlugin):
         UNFILTERED base columns and the predicate runs inside the probe
         (dsx_filter_probe_cols). The ranges are the base columns' cached
         stats either way (_stats_src), so codes and table layout do not
-        change."""
+        change.
+
+        fbuild "l"/"r": that side is a pending DeferredFilter and the BUILD
+        side of an INNER join (_fbuild_for). The table is built straight
+        from its unfiltered base columns with the predicate inside the build
+        (dsx_hash_build_cols), so its row ids index the base columns and
+        the build-side sources below are the base columns too, for the
+        fused probe and for the duplicate-key fallback alike. A
+        materialized build side takes the same entry with an empty
+        predicate; physical/filter_build.py lists what declines."""
+        if fbuild is not None and table is not None:
+            # cannot happen: a group-join attempt materializes its build side
+            runtime.hash_table_free(table)
+            table = None
+        given = {"l": dc_lhs, "r": dc_rhs}
         S = self._fused_setup(runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                              join_type, fprobe)
+                              join_type, fprobe, fbuild)
         pending = S.pending if S is not None else None
         if table is not None and (pending is None
                                   or len(S.fp_cols) > rt.MAX_COLS):
@@ -1195,11 +1271,29 @@ class DaskJoinPlugin(BaseRelPlugin):
         pending, dc_lhs, dc_rhs = S.pending, S.dc_lhs, S.dc_rhs
         if S.fp_cols is not None and len(S.fp_cols) > rt.MAX_COLS:
             # 16 program + key columns at most, else filter first
+            given[fprobe] = DataContainer(pending.table,
+                                          pending.column_container)
             return self._equi_join_fused(
-                runtime, *self._materialized(fprobe, pending, dc_lhs,
-                                             dc_rhs),
-                lhs_on, rhs_on, join_type, combined, mat_idx, cc_lhs,
-                cc_rhs)
+                runtime, given["l"], given["r"], lhs_on, rhs_on, join_type,
+                combined, mat_idx, cc_lhs, cc_rhs, fbuild=fbuild)
+        fbv = self._fb_verdict(
+            join_type, fprobe, "l" in (fprobe, fbuild),
+            "r" in (fprobe, fbuild), dc_lhs.table.num_rows,
+            dc_rhs.table.num_rows, key_rewritten=S.key_rewritten,
+            n_cols=len(S.fb_cols))
+        if fbuild is not None and not fbv:
+            # the build side runs its filter after all: the old path
+            given[fbuild] = DataContainer(S.pending_b.table,
+                                          S.pending_b.column_container)
+            return self._equi_join_fused(
+                runtime, given["l"], given["r"], lhs_on, rhs_on, join_type,
+                combined, mat_idx, cc_lhs, cc_rhs, fprobe=fprobe,
+                build_cols=False)
+        # a WHERE on the build side that could not stay pending has run by
+        # now; its table is built the old way, from the compacted columns
+        fb_side = "l" if S.swap else "r"
+        use_cols = (build_cols and bool(fbv) and not (
+            fbuild is None and isinstance(given[fb_side], DeferredFilter)))
         swap, ranges, ktype = S.swap, S.ranges, S.ktype
         probe_kdc, build_kdc = S.probe_kdc, S.build_kdc
         probe_on, build_on = S.probe_on, S.build_on
@@ -1220,7 +1314,13 @@ class DaskJoinPlugin(BaseRelPlugin):
             (p_items if on_probe else b_items).append((i, col))
         # only the fused filter-probe reads the key-membership filter; a
         # table handed in (a declined group-join's) is that same build
-        if table is None:
+        if table is None and use_cols:
+            table = runtime.hash_build_cols(
+                runtime.make_prog(S.pending_b.prog)
+                if S.pending_b is not None else None,
+                S.fb_cols, S.fb_keys, build_kdc.table.num_rows,
+                code_max=S.fb_space - 1, key_filter=pending is not None)
+        elif table is None:
             bcodes, bval, bkeep, space = self._key_codes(
                 runtime, build_kdc, build_on, ranges)
             table = runtime.hash_build(bcodes, bval, code_max=space - 1,
@@ -1849,10 +1949,22 @@ class DaskAggregatePlugin(BaseRelPlugin):
             kcols.append(build_cols[S.build_on[i]] if kind == "key"
                          else src_col(g))
             group_meta.append((named[e.getIndex()][1], src_col(g)))
-        bcodes, bval, bkeep, space = jp._key_codes(
-            runtime, S.build_kdc, S.build_on, S.ranges)
-        table = runtime.hash_build(bcodes, bval, code_max=space - 1,
-                                   key_filter=True)
+        # the build side is materialized here (a pending one has run by now:
+        # the accumulators are sized by the table's build rows), so the
+        # build-from-columns entry takes it with an empty predicate
+        n_b = S.build_kdc.table.num_rows
+        if jp._fb_verdict("inner", fprobe, fprobe == "l", fprobe == "r",
+                          S.dc_lhs.table.num_rows, S.dc_rhs.table.num_rows,
+                          key_rewritten=S.key_rewritten,
+                          n_cols=len(S.fb_cols)):
+            table = runtime.hash_build_cols(
+                None, S.fb_cols, S.fb_keys, n_b, code_max=S.fb_space - 1,
+                key_filter=True)
+        else:
+            bcodes, bval, bkeep, space = jp._key_codes(
+                runtime, S.build_kdc, S.build_on, S.ranges)
+            table = runtime.hash_build(bcodes, bval, code_max=space - 1,
+                                       key_filter=True)
         try:
             res = runtime.filter_probe_groupby(
                 table, runtime.make_prog(S.pending.prog), fp_cols, S.fp_keys,

@@ -549,6 +549,26 @@ class Runtime:
         )
         return t
 
+    def hash_build_cols(self, prog, cols, keyspecs, n, code_max=0,
+                        key_filter=False):
+        """hash_build straight from source columns (dsx_hash_build_cols):
+        predicate `prog` over `cols` (None or an empty program keeps every
+        row), NULL-key drop, key pack (keyspecs as for keypack, indexing
+        `cols`) and insert in one sweep, without a wait. Row ids in the table
+        index `cols`; the table is sized by n."""
+        parr, plen = prog if prog is not None else (None, 0)
+        t = ct.c_void_p()
+        _check(
+            self.lib,
+            self.lib.dsx_hash_build_cols(
+                self.ctx, parr, ct.c_int(plen), self._cols_array(cols),
+                ct.c_int(len(cols)), self._keyspec_array(keyspecs),
+                ct.c_int(len(keyspecs)), ct.c_int64(n), ct.c_uint64(code_max),
+                ct.c_int(1 if key_filter else 0), ct.byref(t)),
+            "dsx_hash_build_cols",
+        )
+        return t
+
     def hash_table_filter(self, table):
         """(mode, bytes) of the table's key-membership filter: mode 0 none,
         1 exact bitmap, 2 hashed (csrc/join_filter.h)."""

@@ -227,6 +227,23 @@ int dsx_hash_build_filtered(DsxCtx* ctx, const uint64_t* codes,
                             const uint8_t* validity, int64_t n,
                             uint64_t code_max, int key_filter,
                             DsxHashTable** out);
+/* The same table built straight from source columns in one sweep: per row the
+ * predicate program (prog_len == 0: every row; a row is kept only when the
+ * predicate is TRUE), the NULL-key drop over the key columns' validity, the
+ * key pack (keys[j].col indexes `cols`; mode 0 only; codes bit-identical to
+ * dsx_keypack's) and the insert. The stored row id is the row's index in
+ * `cols`, and the table is sized by n (the survivor count is never fetched:
+ * the call copies nothing to the host and waits for nothing). It replaces
+ * dsx_filter_cols -> dsx_keypack -> (dsx_eval for a nullable key) ->
+ * dsx_hash_build_filtered on a build side with a pending WHERE, and
+ * dsx_keypack -> dsx_hash_build_filtered on any other. Both build entries
+ * combine the exact filter's bits per run of neighbouring lanes before the
+ * atomic; DSX_DISABLE_BUILD_RUNCOMBINE=1 (read per call) issues one per row. */
+int dsx_hash_build_cols(DsxCtx* ctx, const DsxInstr* prog, int prog_len,
+                        const DsxColumn* cols, int ncols,
+                        const DsxKeySpec* keys, int nkeys, int64_t n,
+                        uint64_t code_max, int key_filter,
+                        DsxHashTable** out);
 int dsx_hash_table_filter_mode(const DsxHashTable* t);
 int64_t dsx_hash_table_filter_bytes(const DsxHashTable* t);
 /* filtered builds (key_filter != 0) on ctx so far that ended in `mode` */
