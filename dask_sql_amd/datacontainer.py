@@ -118,7 +118,8 @@ class DeferredFilter(DataContainer):
     predicate into the probe sweep (dsx_filter_probe_cols) and never builds
     the filtered table; an INNER join that builds its hash table from it
     fuses the predicate into the build sweep (dsx_hash_build_cols), with row
-    ids that index the base columns (physical/filter_build.py says when);
+    ids that index the base columns; physical/join_plan.py (route: fprobe,
+    fbuild) says which of the two, if either;
     every other consumer reads `.table`, which runs the
     ordinary fused filter (dsx_filter_cols) once and caches the result, so
     it sees exactly what an eager filter would have produced.
@@ -158,6 +159,11 @@ class DeferredFilter(DataContainer):
     def unfiltered(self) -> DataContainer:
         """The base rows under this container's column names."""
         return DataContainer(self.base.table, self.column_container)
+
+
+def pending_filter(dc) -> bool:
+    """dc is a WHERE over a base table that has not run yet."""
+    return isinstance(dc, DeferredFilter) and not dc.materialized
 
 
 class HostDataContainer:

@@ -17,6 +17,26 @@ INT_KINDS = (rt.I64, rt.I32, rt.I8, rt.BOOL8)
 FLOAT_KINDS = (rt.F64, rt.F32)
 
 
+def dicts_of(cols):
+    return [getattr(c, "dictionary", None) for c in cols]
+
+
+def codes_i32(runtime, col):
+    """Dictionary codes as a 4-byte column, the width a gather reads its
+    row ids in. Factorized table columns already are; 8-byte codes out of a
+    groupby or 1-byte codes of a declared dictionary are converted through
+    the host (the VM has no 4-byte output)."""
+    if col.dtype == rt.I32:
+        return col
+    arr, valid = col.to_numpy()
+    arr = np.array(arr, dtype=np.int32)
+    if valid is not None:
+        arr[~valid.astype(bool)] = 0  # NULL rows: any in-range code
+    return runtime.upload_column(
+        arr,
+        None if valid is None else valid.astype(np.uint8), rt.I32)
+
+
 def minmax_cached(runtime, col):
     """Column statistics memo (the reference caches table statistics too —
     datacontainer.py Statistics / statistics.py:21). Derived columns (gather

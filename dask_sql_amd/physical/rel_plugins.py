@@ -14,8 +14,12 @@ from dask_sql_amd import runtime as rt
 from dask_sql_amd.datacontainer import (ColumnContainer, DataContainer,
                                         DeferredFilter, DeviceTable,
                                         HostDataContainer)
-from dask_sql_amd.physical import keys
+from dask_sql_amd.datacontainer import pending_filter as _pending_filter
+from dask_sql_amd.physical import join_plan, keys
 from dask_sql_amd.physical.convert import BaseRelPlugin, RelConverter
+from dask_sql_amd.physical.join import DaskJoinPlugin, source_col
+from dask_sql_amd.physical.keys import codes_i32 as _codes_i32
+from dask_sql_amd.physical.keys import dicts_of as _dicts_of
 from dask_sql_amd.physical.rex import (KB, KF, KI, OP_AND, OP_COL,
                                        OP_IS_NOT_NULL, OP_NOT,
                                        RexCompileError, compile_expr,
@@ -25,27 +29,6 @@ from dask_sql_amd.planner.plan import Call, InputRef
 logger = logging.getLogger(__name__)
 
 _INT_KINDS = keys.INT_KINDS
-
-
-def _dicts_of(cols):
-    return [getattr(c, "dictionary", None) for c in cols]
-
-
-def _codes_i32(runtime, col):
-    """Dictionary codes as a 4-byte column, the width a gather reads its
-    row ids in. Factorized table columns already are. Other widths (8-byte
-    codes out of a groupby — DISTINCT, GROUP BY keys — or 1-byte codes of a
-    declared dictionary) used to be read as if they were 4 bytes wide; the
-    VM has no 4-byte output, so they are converted through the host."""
-    if col.dtype == rt.I32:
-        return col
-    arr, valid = col.to_numpy()
-    arr = np.array(arr, dtype=np.int32)
-    if valid is not None:
-        arr[~valid.astype(bool)] = 0  # NULL rows: any in-range code
-    return runtime.upload_column(
-        arr,
-        None if valid is None else valid.astype(np.uint8), rt.I32)
 
 
 def _gather_table(runtime, dc: DataContainer, sel_ptr, n_sel,
@@ -205,10 +188,6 @@ def _unique_backends(cc):
     return backends
 
 
-def _pending_filter(dc) -> bool:
-    return isinstance(dc, DeferredFilter) and not dc.materialized
-
-
 def _run_deferred_filter(d: DeferredFilter) -> DeviceTable:
     """First `.table` access of a DeferredFilter: the ordinary fused filter
     (dsx_filter_cols) over the base container's columns."""
@@ -242,8 +221,7 @@ def _defer_filter(runtime, dc, condition, context):
     A second WHERE over a pending one joins it as a conjunction: a filter
     keeps a row only when its predicate is TRUE, so (p1 AND p2) keeps
     exactly the rows that p2 keeps of what p1 kept."""
-    import os as _os
-    if _os.environ.get("DSX_DISABLE_FILTERPROBE"):
+    if join_plan.filterprobe_disabled():
         return None
     if _has_udf(condition):
         return None  # UDF nodes evaluate through the host, eagerly
@@ -449,988 +427,6 @@ class DaskProjectPlugin(BaseRelPlugin):
         cc = self.fix_column_to_row_type(cc, rel.getRowType())
         return DataContainer(DeviceTable(out_cols,
                                          num_rows=dc.table.num_rows), cc)
-
-
-class DaskJoinPlugin(BaseRelPlugin):
-    """reference rel/logical/join.py:23-322.
-
-    Equi/residual split mirrors _split_join_condition (:250-322); NULL-key
-    drop (:202-213) is the kernels' validity skip; dd.merge (:241-246)
-    becomes CAS-claim hash build + probe-compaction (k_hash_build/probe);
-    LEFTSEMI falls back to INNER like the reference CPU path (:78-79);
-    residual applied via filter_or_scalar (:169-181); FULL OUTER composed
-    from LEFT + unmatched-build sweep, NaN-filled (test_join.py:55-65)."""
-
-    class_name = "Join"
-
-    JOIN_TYPE_MAPPING = {
-        "INNER": "inner", "LEFT": "left", "RIGHT": "right", "FULL": "outer",
-        "LEFTSEMI": "inner",  # reference join.py:78-79 (CPU)
-        "LEFTANTI": "leftanti", "CROSS": "cross",
-    }
-
-    def convert(self, rel, context, inputs=None, table=None):
-        """inputs: the two converted input containers, when a caller (the
-        aggregate's group-join attempt) has converted them already; table:
-        the hash table that caller built over this join's build side with
-        the key filter (_fused_setup's sides), handed over for the fused
-        filter-probe join to use and free."""
-        runtime = context._get_runtime()
-        J = self._prepare(rel, *(inputs if inputs is not None
-                                 else self.assert_inputs(rel, 2, context)))
-        join, dc_lhs, dc_rhs = J.join, J.dc_lhs, J.dc_rhs
-        cc_lhs, cc_rhs, n_lhs_cols = J.cc_lhs, J.cc_rhs, J.n_lhs_cols
-        join_type, residual = J.join_type, J.residual
-        lhs_on, rhs_on = J.lhs_on, J.rhs_on
-
-        if (join_type == "leftanti" and getattr(join, "null_aware", False)
-                and rhs_on):
-            # NOT IN three-valued logic: any NULL in the subquery output
-            # makes `x NOT IN (...)` non-TRUE for every row → empty result
-            rcols0 = dc_rhs.backend_cols()
-            for ri in rhs_on:
-                col = rcols0[ri]
-                if col.validity:
-                    _, _, nn = keys.minmax_cached(runtime, col)
-                    if nn < dc_rhs.table.num_rows:
-                        return self._empty_output(rel, runtime, dc_lhs,
-                                                  cc_lhs)
-
-        force_l = join_type in ("outer", "right")
-        force_r = join_type in ("left", "outer")
-        combined, out_idx, mat_idx = J.combined, J.out_idx, J.mat_idx
-        null_eq = J.null_eq
-        from dask_sql_amd.planner.prune import _expr_refs, _remap
-
-        # FUSED PATH: emit writes the output columns directly — no pair
-        # vectors, no per-column gathers (k_hash_probe_mat)
-        import os as _os
-        gathered = None
-        # RADIX PATH first (VERDICT r1 #3): once the flat probe table
-        # outgrows the XCD L2, partition both sides and probe LDS-resident
-        # bucket tables instead (dsx_radix_join)
-        fprobe = self._fprobe_for(J)
-        # a pending build side that the fused path builds straight from its
-        # base columns; the radix gate has declined such a join already
-        fbuild = self._fbuild_for(J, fprobe)
-        if (fprobe is None and fbuild is None
-                and lhs_on and not residual and not null_eq
-                and len(mat_idx) <= 16
-                and not _os.environ.get("DSX_DISABLE_RADIX")
-                and join_type in ("inner", "left", "right", "leftanti")):
-            gathered, n_out = self._radix_join(
-                runtime, dc_lhs, dc_rhs, lhs_on, rhs_on, join_type,
-                combined, mat_idx, cc_lhs, cc_rhs)
-        if (gathered is None
-                and lhs_on and not residual and not null_eq
-                and len(mat_idx) <= 16
-                and not _os.environ.get("DSX_DISABLE_JOINFUSE")
-                and join_type in ("inner", "left", "right", "leftanti")):
-            gathered, n_out = self._equi_join_fused(
-                runtime, dc_lhs, dc_rhs, lhs_on, rhs_on, join_type,
-                combined, mat_idx, cc_lhs, cc_rhs, fprobe=fprobe,
-                table=table, fbuild=fbuild)
-            table = None  # freed there
-        if table is not None:
-            runtime.hash_table_free(table)
-
-        if gathered is None:
-            if lhs_on:
-                if residual and join_type == "leftanti":
-                    # ANTI with extra condition: keep lhs rows with NO rhs
-                    # match satisfying key AND residual (join.py:169-181
-                    # composed with the anti semantics of :78-90)
-                    pairs, n_out = self._anti_residual(
-                        runtime, dc_lhs, dc_rhs, lhs_on, rhs_on, residual,
-                        cc_lhs, cc_rhs, n_lhs_cols)
-                    residual = []
-                else:
-                    pairs, n_out = self._equi_join(runtime, dc_lhs, dc_rhs,
-                                                   lhs_on, rhs_on, join_type,
-                                                   null_equal=null_eq)
-            else:
-                pairs, n_out = self._cross_join(runtime, dc_lhs, dc_rhs,
-                                                join_type)
-            probe_sel, build_sel = pairs
-
-            res_refs = set()
-            for r in residual:
-                _expr_refs(r, res_refs)
-            mat_idx = sorted(set(out_idx) | res_refs)
-            gathered = {}
-            for i in mat_idx:
-                side, frontend = combined[i]
-                if side == "l":
-                    col = dc_lhs.table.col(
-                        cc_lhs.get_backend_by_frontend_name(frontend))
-                    g = runtime.gather(col, probe_sel.data, n_out, force_l)
-                else:
-                    col = dc_rhs.table.col(
-                        cc_rhs.get_backend_by_frontend_name(frontend))
-                    g = runtime.gather(col, build_sel.data, n_out, force_r)
-                if getattr(col, "dictionary", None) is not None:
-                    g.dictionary = col.dictionary
-                g._stats_src = col
-                gathered[i] = g
-
-        # residual filter (join.py:169-181) over the combined row, with
-        # InputRefs densified to the materialized set
-        if residual:
-            cond = residual[0]
-            for r in residual[1:]:
-                cond = Call("AND", [cond, r])
-            dense = {i: pos for pos, i in enumerate(mat_idx)}
-            cond = _remap(cond, dense)
-            cols_list = [gathered[i] for i in mat_idx]
-            s = scalar_literal(cond)
-            if s is not None:
-                if not s:
-                    empty = runtime.empty_column(0, rt.I32)
-                    gathered = {i: runtime.gather(gathered[i], empty.data, 0)
-                                for i in mat_idx}
-                    n_out = 0
-            else:
-                prog, _ = compile_expr(cond, cols_list, _dicts_of(cols_list))
-                sel_ptr, count = runtime.filter(runtime.make_prog(prog),
-                                                cols_list, n_out)
-                sel = runtime.wrap_sel(sel_ptr, count)
-                new_g = {}
-                for i in out_idx:
-                    col = gathered[i]
-                    g = runtime.gather(col, sel.data, count,
-                                       bool(col.validity))
-                    if getattr(col, "dictionary", None) is not None:
-                        g.dictionary = col.dictionary
-                    g._stats_src = col
-                    new_g[i] = g
-                gathered = new_g
-                n_out = count
-
-        row_type = rel.getRowType()
-        field_names = [str(f) for f in row_type.getFieldNames()]
-        assert len(field_names) == len(out_idx), (field_names, out_idx)
-        out_cols = {}
-        mapping = {}
-        for name, i in zip(field_names, out_idx):
-            backend = f"j{i}__{name}"
-            out_cols[backend] = gathered[i]
-            mapping[name] = backend
-        cc = ColumnContainer(field_names, mapping)
-        return DataContainer(DeviceTable(out_cols, num_rows=n_out), cc)
-
-    def _prepare(self, rel, dc_lhs, dc_rhs):
-        """What the plan says about this join, over its two converted
-        inputs: unique column names, the join type, the split condition and
-        the columns to materialize."""
-        from types import SimpleNamespace
-        join = rel.join()
-        cc_lhs = dc_lhs.column_container.make_unique("lhs")
-        cc_rhs = dc_rhs.column_container.make_unique("rhs")
-        dc_lhs = dc_lhs.with_columns(cc_lhs)
-        dc_rhs = dc_rhs.with_columns(cc_rhs)
-        n_lhs_cols = len(cc_lhs.columns)
-
-        join_type = self.JOIN_TYPE_MAPPING[str(join.getJoinType())]
-
-        condition = join.getCondition()
-        lhs_on, rhs_on, residual = [], [], []
-        if condition is not None:
-            lhs_on, rhs_on, residual = self._split_join_condition(
-                condition, n_lhs_cols)
-
-        # materialize only columns the plan consumes (output_indices from the
-        # pruning pass) plus residual-referenced temporaries
-        combined = [("l", f) for f in cc_lhs.columns]
-        keep_rhs = join_type not in ("leftanti",)
-        if keep_rhs:
-            combined += [("r", f) for f in cc_rhs.columns]
-        out_idx = join.output_indices if getattr(join, "output_indices",
-                                                 None) is not None \
-            else list(range(len(combined)))
-        if (getattr(join, "output_indices", None) is None
-                and str(join.getJoinType()) == "LEFTSEMI"):
-            # unpruned SEMI join (e.g. below a UNION): lhs columns only
-            out_idx = list(range(n_lhs_cols))
-        return SimpleNamespace(
-            join=join, dc_lhs=dc_lhs, dc_rhs=dc_rhs, cc_lhs=cc_lhs,
-            cc_rhs=cc_rhs, n_lhs_cols=n_lhs_cols, join_type=join_type,
-            lhs_on=lhs_on, rhs_on=rhs_on, residual=residual,
-            combined=combined, out_idx=out_idx,
-            mat_idx=sorted(set(out_idx)),
-            null_eq=bool(getattr(join, "null_equal", False)))
-
-    def _fprobe_for(self, J):
-        """FILTER-PROBE: a probe side that is a still-pending WHERE over a
-        base table runs its predicate inside the probe sweep
-        (dsx_filter_probe_cols); DSX_DISABLE_FILTERPROBE=1 restores the
-        separate filter → keypack → probe passes. Returns the probe side
-        ("l"/"r") or None."""
-        import os as _os
-        if (J.join_type == "inner" and J.lhs_on and not J.residual
-                and not J.null_eq and len(J.mat_idx) <= 16
-                and not _os.environ.get("DSX_DISABLE_JOINFUSE")
-                and not _os.environ.get("DSX_DISABLE_FILTERPROBE")):
-            return self._filter_probe_side(J.dc_lhs, J.dc_rhs)
-        return None
-
-    @staticmethod
-    def _fb_verdict(join_type, fprobe, pend_l, pend_r, n_l, n_r,
-                    fusable=True, **setup_facts):
-        """physical/filter_build.verdict with the knobs read now."""
-        import os as _os
-
-        from dask_sql_amd.physical import filter_build as fb
-        radix = None if _os.environ.get("DSX_DISABLE_RADIX") else int(
-            _os.environ.get("DSX_RADIX_MIN_BUILD", 8_000_000))
-        return fb.verdict(
-            join_type=join_type, fusable=fusable, pend_l=pend_l,
-            pend_r=pend_r, n_l=n_l, n_r=n_r, probe_side=fprobe,
-            radix_min_build=radix, cap=fb.max_rows(), knob_off=fb.disabled(),
-            min_rows=fb.min_rows(),
-            max_cols=rt.MAX_COLS, **setup_facts)
-
-    def _fbuild_for(self, J, fprobe):
-        """FILTER-BUILD: the side ("l"/"r") whose still-pending WHERE runs
-        inside the hash build (dsx_hash_build_cols) because it is the build
-        side of a fused INNER join, or None (physical/filter_build.py)."""
-        import os as _os
-        pend_l, pend_r = _pending_filter(J.dc_lhs), _pending_filter(J.dc_rhs)
-        if not (pend_l or pend_r):
-            return None
-        fusable = bool(
-            J.lhs_on and not J.residual and not J.null_eq
-            and len(J.mat_idx) <= 16
-            and not _os.environ.get("DSX_DISABLE_JOINFUSE")
-            and J.join_type in ("inner", "left", "right", "leftanti"))
-        n_l = J.dc_lhs.max_rows if pend_l else J.dc_lhs.table.num_rows
-        n_r = J.dc_rhs.max_rows if pend_r else J.dc_rhs.table.num_rows
-        v = self._fb_verdict(J.join_type, fprobe, pend_l, pend_r, n_l, n_r,
-                             fusable=fusable)
-        if not v:
-            logger.debug("join: build side filters first (%s)", v.reason)
-        return v.side if v and v.pending else None
-
-    # -- helpers ------------------------------------------------------------
-    def _empty_output(self, rel, runtime, dc_lhs, cc_lhs):
-        row_type = rel.getRowType()
-        field_names = [str(f) for f in row_type.getFieldNames()]
-        join = rel.join()
-        out_idx = join.output_indices \
-            if getattr(join, "output_indices", None) is not None \
-            else list(range(len(field_names)))
-        empty = runtime.empty_column(0, rt.I32)
-        out_cols = {}
-        mapping = {}
-        lcols = dc_lhs.backend_cols()
-        for name, oi in zip(field_names, out_idx):
-            src = lcols[oi] if oi < len(lcols) else lcols[0]
-            i = oi
-            g = runtime.gather(src, empty.data, 0)
-            if getattr(src, "dictionary", None) is not None:
-                g.dictionary = src.dictionary
-            backend = f"j{i}__{name}"
-            out_cols[backend] = g
-            mapping[name] = backend
-        cc = ColumnContainer(field_names, mapping)
-        return DataContainer(DeviceTable(out_cols, num_rows=0), cc)
-
-    def _anti_residual(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                       residual, cc_lhs, cc_rhs, n_lhs_cols):
-        """LEFT ANTI with a residual condition: inner pairs, residual filter
-        on the pairs, then the complement of the surviving probe ids (host
-        complement — this shape is rare and the surviving-id set is small)."""
-        from dask_sql_amd.planner.prune import _expr_refs, _remap
-        (pi, bi), n_i = self._equi_join(runtime, dc_lhs, dc_rhs, lhs_on,
-                                        rhs_on, "inner")
-        n_l = dc_lhs.table.num_rows
-        matched = np.empty(0, dtype=np.uint32)
-        if n_i:
-            refs = set()
-            for r in residual:
-                _expr_refs(r, refs)
-            refs = sorted(refs)
-            cols_list = []
-            for i in refs:
-                if i < n_lhs_cols:
-                    col = dc_lhs.table.col(cc_lhs.get_backend_by_frontend_name(
-                        cc_lhs.columns[i]))
-                    g = runtime.gather(col, pi.data, n_i)
-                else:
-                    col = dc_rhs.table.col(cc_rhs.get_backend_by_frontend_name(
-                        cc_rhs.columns[i - n_lhs_cols]))
-                    g = runtime.gather(col, bi.data, n_i)
-                if getattr(col, "dictionary", None) is not None:
-                    g.dictionary = col.dictionary
-                cols_list.append(g)
-            cond = residual[0]
-            for r in residual[1:]:
-                cond = Call("AND", [cond, r])
-            cond = _remap(cond, {i: pos for pos, i in enumerate(refs)})
-            s = scalar_literal(cond)
-            if s is None:
-                prog, _ = compile_expr(cond, cols_list, _dicts_of(cols_list))
-                sel_ptr, cnt = runtime.filter(runtime.make_prog(prog),
-                                              cols_list, n_i)
-                surv = runtime.wrap_sel(sel_ptr, cnt)
-                if cnt:
-                    pid = runtime.gather(pi, surv.data, cnt)
-                    matched = np.empty(cnt, dtype=np.uint32)
-                    runtime._download(pid.data, matched)
-            elif s:
-                matched = np.empty(n_i, dtype=np.uint32)
-                runtime._download(pi.data, matched)
-        mask = np.ones(n_l, dtype=bool)
-        if len(matched):
-            mask[matched.astype(np.int64)] = False
-        anti = np.flatnonzero(mask).astype(np.uint32)
-        sel = runtime.upload_column(anti, dtype=rt.I32)
-        return (sel, sel), len(anti)
-
-    def _reconcile_dict_keys(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on):
-        """String join keys: the reference merges on the STRINGS
-        (join.py:241-246 dd.merge on object columns); our per-table
-        factorization makes raw dict codes incomparable across tables, so
-        rhs key codes are remapped into the lhs dictionary space on device
-        (host builds the small code→code map, one gather applies it;
-        strings absent from the lhs dictionary get a sentinel code that can
-        never match). Returns a shadow (dc_rhs, rcols) for key building only
-        — materialization keeps the original codes + dictionary."""
-        lcols = dc_lhs.backend_cols()
-        rcols = dc_rhs.backend_cols()
-        sub = {}
-        for li, ri in zip(lhs_on, rhs_on):
-            dl = getattr(lcols[li], "dictionary", None)
-            dr = getattr(rcols[ri], "dictionary", None)
-            if dl is None and dr is None:
-                continue
-            if (dl is None) != (dr is None):
-                raise RexCompileError(
-                    "join key pairs a string column with a non-string column")
-            if dl is dr or list(dl) == list(dr):
-                continue  # same dictionary → codes already comparable
-            index = {s: c for c, s in enumerate(dl)}
-            miss = len(dl)  # sentinel: never present on the lhs side
-            m = np.array([index.get(s, miss) for s in dr], dtype=np.int64)
-            map_col = runtime.upload_column(m)
-            codes = _codes_i32(runtime, rcols[ri])
-            g = runtime.gather(map_col, codes.data,
-                               dc_rhs.table.num_rows)
-            rem = rt.DeviceColumn(runtime, g.data, rcols[ri].validity,
-                                  g.len, rt.I64, owner=False,
-                                  keep_alive=(g, rcols[ri], map_col, codes))
-            rem.dictionary = dl
-            sub[ri] = rem
-        if not sub:
-            return dc_rhs, rcols
-        cc = dc_rhs.column_container
-        cols2 = dict(dc_rhs.table.columns)
-        for ri, col in sub.items():
-            cols2[cc.get_backend_by_frontend_name(cc.columns[ri])] = col
-        dc2 = DataContainer(DeviceTable(cols2), cc)
-        return dc2, dc2.backend_cols()
-
-    def _key_codes(self, runtime, dc, on, ranges, null_flags=None):
-        """Build i64 code column + optional validity for join keys.
-
-        null_flags (FULL OUTER only): per-key bools — NULL packs as its own
-        code slot so NULL keys MATCH each other, which is what the reference
-        produces (pandas merge how="outer" matches NA keys; join.py:202-213
-        drops NULL keys only for inner/left/right/semi). Returns
-        (codes, validity_ptr, keep, key_space)."""
-        cols = dc.backend_cols()
-        if null_flags is not None:
-            keyspecs = [(idx, mn, rng, nf) for (idx, (mn, rng)), nf
-                        in zip(zip(on, ranges), null_flags)]
-            codes, space = runtime.keypack(cols, keyspecs,
-                                           dc.table.num_rows)
-            return codes, None, None, space
-        keyspecs = []
-        for (idx, (mn, rng)) in zip(on, ranges):
-            keyspecs.append((idx, mn, rng, False))
-        codes, space = runtime.keypack(cols, keyspecs, dc.table.num_rows)
-        validity_ptr = None
-        keep = None
-        if any(cols[i].validity for i in on):
-            # combined key validity (NULL-key semantics, join.py:202-213)
-            expr_prog = []
-            first = True
-            for i in on:
-                expr_prog += [(OP_COL, i, 0), (OP_IS_NOT_NULL, 0, 0)]
-                if not first:
-                    expr_prog.append((OP_AND, 0, 0))
-                first = False
-            vcol = runtime.eval(runtime.make_prog(expr_prog), cols,
-                                dc.table.num_rows, rt.BOOL8,
-                                with_validity=False)
-            validity_ptr = vcol.data
-            keep = vcol
-        return codes, validity_ptr, keep, space
-
-    def _densify_join_float_key(self, runtime, lcol, rcol):
-        """Float equi-join keys: give every distinct f64 bit-pattern ONE
-        dense integer id, consistent across BOTH sides, by running the
-        bits-mode groupby over the concatenation and joining the ids back
-        per row (same primitive chain as _densify_float_keys). NaN keys
-        share an id — pandas merge matches NaN with NaN; NULL rows keep
-        the original validity so the normal NULL-key drop applies.
-        Returns (lid, rid, n_distinct)."""
-        n_l, n_r = lcol.len, rcol.len
-        cat = runtime.concat_columns([lcol, rcol], rt.F64)
-        oc, ov, on_, G = runtime.hash_groupby(
-            [cat], n_l + n_r, [(0, 0, 0, True, 1)], None, [])
-        runtime._free(ov)
-        runtime._free(on_)
-        bcol = rt.DeviceColumn(runtime, oc, None, max(G, 1), rt.I64,
-                               owner=True)
-        pcodes, _ = runtime.keypack([cat], [(0, 0, 0, True, 1)], n_l + n_r)
-        table = runtime.hash_build(bcol, None, code_max=0)
-        try:
-            p, b, cnt = runtime.hash_probe(table, pcodes, rt.JOIN_INNER,
-                                           None)
-            psel = runtime.wrap_sel(p, cnt)
-            bsel = runtime.wrap_sel(b, cnt)
-            assert cnt == n_l + n_r, (cnt, n_l + n_r)
-            fid = runtime.scatter_rows(bsel, psel.data, cnt, n_l + n_r,
-                                       with_validity=False)
-        finally:
-            runtime.hash_table_free(table)
-        keep = (fid, lcol, rcol)
-        # fid holds the scattered build positions: 4-byte ids like bsel
-        assert fid.dtype == rt.I32, fid.dtype
-        lid = rt.DeviceColumn(runtime, fid.data, lcol.validity, n_l,
-                              rt.I32, owner=False, keep_alive=keep)
-        rid = rt.DeviceColumn(runtime, fid.data + 4 * n_l, rcol.validity,
-                              n_r, rt.I32, owner=False, keep_alive=keep)
-        return lid, rid, G
-
-    def _equi_join(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on, join_type,
-                   null_equal=False):
-        lcols = dc_lhs.backend_cols()
-        rcols = dc_rhs.backend_cols()
-        for li, ri in zip(lhs_on, rhs_on):
-            lk, rk = lcols[li].dtype, rcols[ri].dtype
-            if (lk in _INT_KINDS) != (rk in _INT_KINDS):
-                raise RexCompileError("join key type mismatch (int vs "
-                                      "float) — cast one side first")
-            if lk == rt.F32 or rk == rt.F32:
-                raise RexCompileError("float32 join keys: cast to DOUBLE")
-            if lk not in _INT_KINDS and lk != rt.F64:
-                raise RexCompileError("unsupported join key dtype")
-        dc_rhs, rcols = self._reconcile_dict_keys(runtime, dc_lhs, dc_rhs,
-                                                  lhs_on, rhs_on)
-        # f64 keys densify to consistent integer ids (single OR composite)
-        float_pairs = [j for j, (li, ri) in enumerate(zip(lhs_on, rhs_on))
-                       if lcols[li].dtype == rt.F64]
-        dense_ranges = {}
-        if float_pairs:
-            lcols = list(lcols)
-            rcols = list(rcols)
-            lhs_on = list(lhs_on)
-            rhs_on = list(rhs_on)
-            for j in float_pairs:
-                lid, rid, G = self._densify_join_float_key(
-                    runtime, lcols[lhs_on[j]], rcols[rhs_on[j]])
-                lcols.append(lid)
-                rcols.append(rid)
-                lhs_on[j] = len(lcols) - 1
-                rhs_on[j] = len(rcols) - 1
-                dense_ranges[j] = (0, max(G, 1))
-            import types as _types
-            dc_lhs = _types.SimpleNamespace(
-                backend_cols=lambda c=lcols: c,
-                table=_types.SimpleNamespace(
-                    num_rows=dc_lhs.table.num_rows))
-            dc_rhs = _types.SimpleNamespace(
-                backend_cols=lambda c=rcols: c,
-                table=_types.SimpleNamespace(
-                    num_rows=dc_rhs.table.num_rows))
-        # combined ranges over both sides so codes are comparable
-        ranges = []
-        for j, (li, ri) in enumerate(zip(lhs_on, rhs_on)):
-            if j in dense_ranges:
-                ranges.append(dense_ranges[j])
-                continue
-            ranges.append(keys.joint_range(runtime, lcols[li], rcols[ri]))
-
-        # build on the smaller side for INNER (what the reference gets from
-        # dask's merge internals + JoinReorder, src/sql/optimizer/join_reorder.rs)
-        swap = join_type == "right" or (
-            join_type == "inner"
-            and dc_lhs.table.num_rows < dc_rhs.table.num_rows)
-        if swap:
-            probe_dc, build_dc = dc_rhs, dc_lhs
-            probe_on, build_on = rhs_on, lhs_on
-            ktype = rt.JOIN_LEFT if join_type == "right" else rt.JOIN_INNER
-        else:
-            probe_dc, build_dc = dc_lhs, dc_rhs
-            probe_on, build_on = lhs_on, rhs_on
-            ktype = {
-                "inner": rt.JOIN_INNER, "left": rt.JOIN_LEFT,
-                "outer": rt.JOIN_LEFT, "leftanti": rt.JOIN_LEFTANTI,
-            }[join_type]
-
-        # FULL OUTER: NULL keys get their own code slot so they MATCH each
-        # other — the reference keeps both sides' NULL-key rows and pandas
-        # merge how="outer" matches NA keys (join.py:202-213 drops NULL keys
-        # only for inner/left/right/semi). ADVICE r1 (medium).
-        null_flags = None
-        if join_type == "outer" or null_equal:
-            # null_equal: INTERSECT/EXCEPT semi/anti joins use DataFusion's
-            # null_equals_null — NULL keys pack into their own slot and
-            # match each other instead of being dropped
-            pkc, bkc = probe_dc.backend_cols(), build_dc.backend_cols()
-            null_flags = [
-                bool(pkc[pi].validity) or bool(bkc[bi].validity)
-                for pi, bi in zip(probe_on, build_on)]
-        bcodes, bval, bkeep, bspace = self._key_codes(
-            runtime, build_dc, build_on, ranges, null_flags)
-        pcodes, pval, pkeep, _ = self._key_codes(
-            runtime, probe_dc, probe_on, ranges, null_flags)
-        table = runtime.hash_build(bcodes, bval, code_max=bspace - 1)
-        try:
-            p_ptr, b_ptr, count = runtime.hash_probe(
-                table, pcodes, ktype, pval,
-                mark_matched=(join_type == "outer"))
-            probe_sel = runtime.wrap_sel(p_ptr, count)
-            build_sel = runtime.wrap_sel(b_ptr, count)
-            if join_type == "outer":
-                # FULL = LEFT + unmatched build rows (test_join.py:46-66)
-                ub_ptr, u_count = runtime.hash_unmatched(table)
-                if u_count:
-                    ub = runtime.wrap_sel(ub_ptr, u_count)
-                    p_host = np.empty(count + u_count, dtype=np.uint32)
-                    b_host = np.empty(count + u_count, dtype=np.uint32)
-                    tmp = np.empty(count, dtype=np.uint32)
-                    runtime._download(probe_sel.data, tmp)
-                    p_host[:count] = tmp
-                    runtime._download(build_sel.data, tmp)
-                    b_host[:count] = tmp
-                    utmp = np.empty(u_count, dtype=np.uint32)
-                    runtime._download(ub.data, utmp)
-                    p_host[count:] = rt.NULL_IDX
-                    b_host[count:] = utmp
-                    probe_sel = runtime.upload_column(p_host, dtype=rt.I32)
-                    build_sel = runtime.upload_column(b_host, dtype=rt.I32)
-                    count += u_count
-                else:
-                    runtime._free(ub_ptr)
-        finally:
-            runtime.hash_table_free(table)
-        if swap:
-            probe_sel, build_sel = build_sel, probe_sel
-        return (probe_sel, build_sel), count
-
-    def _radix_join(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                    join_type, combined, mat_idx, cc_lhs, cc_rhs):
-        """Radix-partitioned equijoin (dsx_radix_join — VERDICT r1 #3, the
-        north star's LDS-staged build/probe). Worth the partition passes
-        only when the flat probe table would spill the XCD L2: gated on
-        build/probe sizes (DSX_RADIX_MIN_BUILD/_MIN_PROBE). Returns
-        ({combined_idx: DeviceColumn}, n_out) or (None, 0) → caller tries
-        the flat fused path."""
-        import os as _os
-        n_l, n_r = dc_lhs.table.num_rows, dc_rhs.table.num_rows
-        min_build = int(_os.environ.get("DSX_RADIX_MIN_BUILD", 8_000_000))
-        min_probe = int(_os.environ.get("DSX_RADIX_MIN_PROBE", 4_000_000))
-        # swap exactly like the fused path: build on rhs, except RIGHT
-        # (probe = rhs) and INNER on the smaller side
-        swap = join_type == "right" or (
-            join_type == "inner" and n_l < n_r)
-        nb_, np_ = (n_l, n_r) if swap else (n_r, n_l)
-        if nb_ < min_build or np_ < min_probe:
-            return None, 0
-        lcols = dc_lhs.backend_cols()
-        rcols = dc_rhs.backend_cols()
-        for i in lhs_on:
-            if lcols[i].dtype not in _INT_KINDS:
-                return None, 0  # float keys: pair path densifies them
-        for i in rhs_on:
-            if rcols[i].dtype not in _INT_KINDS:
-                return None, 0
-        kdc_rhs, krcols = self._reconcile_dict_keys(runtime, dc_lhs, dc_rhs,
-                                                    lhs_on, rhs_on)
-        ranges = []
-        for li, ri in zip(lhs_on, rhs_on):
-            ranges.append(keys.joint_range(runtime, lcols[li], krcols[ri]))
-        if swap:
-            probe_dc, build_dc = kdc_rhs, dc_lhs
-            probe_on, build_on = rhs_on, lhs_on
-            ktype = rt.JOIN_LEFT if join_type == "right" else rt.JOIN_INNER
-        else:
-            probe_dc, build_dc = dc_lhs, kdc_rhs
-            probe_on, build_on = lhs_on, rhs_on
-            ktype = {"inner": rt.JOIN_INNER, "left": rt.JOIN_LEFT,
-                     "leftanti": rt.JOIN_LEFTANTI}[join_type]
-        bcols = build_dc.backend_cols()
-        pcols = probe_dc.backend_cols()
-        # NULL keys: pack them into their own code slot (nullable flag,
-        # both sides identically) and DROP build-side NULL keys with a
-        # predicate — code 0 then never matches, so INNER skips NULL-key
-        # probe rows and LEFT null-extends them, exactly join.py:202-213
-        null_flags = [bool(pcols[pi].validity) or bool(bcols[bi].validity)
-                      for pi, bi in zip(probe_on, build_on)]
-        keyspecs_b = [(bi, mn, rng, nf) for bi, (mn, rng), nf
-                      in zip(build_on, ranges, null_flags)]
-        keyspecs_p = [(pi, mn, rng, nf) for pi, (mn, rng), nf
-                      in zip(probe_on, ranges, null_flags)]
-        bpred = []
-        for bi in build_on:
-            if bcols[bi].validity:
-                bpred += [(OP_COL, bi, 0), (OP_IS_NOT_NULL, 0, 0)]
-                if len(bpred) > 2:
-                    bpred.append((OP_AND, 0, 0))
-        # output spec: mat_idx over `combined` → (side, col-in-side-array).
-        # The arrays passed to C start as the (possibly dict-remapped) key
-        # views; payloads whose original column was substituted by the
-        # remap are APPENDED so outputs keep the original codes.
-        probe_is_l = not swap
-        b_arr = list(bcols)
-        p_arr = list(pcols)
-        out_specs = []
-        srcs = []
-        force_bv = ktype == rt.JOIN_LEFT
-        for i in mat_idx:
-            side, frontend = combined[i]
-            if side == "l":
-                col = dc_lhs.table.col(
-                    cc_lhs.get_backend_by_frontend_name(frontend))
-                on_probe = probe_is_l
-            else:
-                col = dc_rhs.table.col(
-                    cc_rhs.get_backend_by_frontend_name(frontend))
-                on_probe = not probe_is_l
-            arr = p_arr if on_probe else b_arr
-            ci = next((j for j, c in enumerate(arr) if c is col), None)
-            if ci is None:
-                arr.append(col)
-                ci = len(arr) - 1
-            need_valid = bool(col.validity) or (not on_probe and force_bv)
-            out_specs.append((0 if on_probe else 1, ci, need_valid))
-            srcs.append(col)
-        if len(b_arr) > 16 or len(p_arr) > 16:
-            return None, 0  # DSX_MAX_COLS — flat path handles wide tables
-        res = runtime.radix_join(
-            b_arr, build_dc.table.num_rows, keyspecs_b, keyspecs_p, bpred,
-            p_arr, probe_dc.table.num_rows, ktype, out_specs)
-        if res is None:
-            return None, 0
-        cols_out, n_out = res
-        gathered = {}
-        for i, src, col in zip(mat_idx, srcs, cols_out):
-            if getattr(src, "dictionary", None) is not None:
-                col.dictionary = src.dictionary
-            col._stats_src = src
-            gathered[i] = col
-        return gathered, n_out
-
-    @staticmethod
-    def _filter_probe_side(dc_lhs, dc_rhs):
-        """Which side ("l"/"r") an INNER join probes with a pending WHERE
-        fused in, or None. The probe side is the larger one; a pending
-        filter's row count is not known before it runs, so it stands in with
-        its base table's. A pending side that comes out as the build side
-        stays pending too where _fbuild_for takes it (its WHERE then runs
-        inside the hash build, dsx_hash_build_cols) and materializes
-        otherwise. The radix path keeps priority: where both
-        sides could pass its build-size gate the filters run first, as
-        before, and the gate sees the real counts."""
-        import os as _os
-        pend_l, pend_r = _pending_filter(dc_lhs), _pending_filter(dc_rhs)
-        if not (pend_l or pend_r):
-            return None
-        n_l = dc_lhs.max_rows if pend_l else dc_lhs.table.num_rows
-        n_r = dc_rhs.max_rows if pend_r else dc_rhs.table.num_rows
-        if (not _os.environ.get("DSX_DISABLE_RADIX") and min(n_l, n_r) >= int(
-                _os.environ.get("DSX_RADIX_MIN_BUILD", 8_000_000))):
-            return None
-        if n_l < n_r:  # same rule as the swap below: probe with the larger
-            return "r" if pend_r else None
-        return "l" if pend_l else None
-
-    def _fused_setup(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                     join_type, fprobe, fbuild=None):
-        """Sides, key ranges and the fused entries' column lists for
-        _equi_join_fused and the aggregate's group-join; None when a key is
-        not an integer kind. fp_cols / fp_keys (pending probe side only): the
-        probe-side program columns plus key columns in ONE list, and the
-        key specs indexing it; the caller checks the list's length. fb_cols /
-        fb_keys: the same for the build side and dsx_hash_build_cols, with
-        the program columns of a pending build side (fbuild) or none;
-        key_rewritten says that the build key is a dictionary remap."""
-        from types import SimpleNamespace
-        pending = {"l": dc_lhs, "r": dc_rhs}.get(fprobe)
-        pending_b = {"l": dc_lhs, "r": dc_rhs}.get(fbuild)
-        if "l" in (fprobe, fbuild):
-            dc_lhs = dc_lhs.unfiltered()
-        if "r" in (fprobe, fbuild):
-            dc_rhs = dc_rhs.unfiltered()
-        lcols = dc_lhs.backend_cols()
-        rcols = dc_rhs.backend_cols()
-        for i in lhs_on:
-            if lcols[i].dtype not in _INT_KINDS:
-                return None
-        for i in rhs_on:
-            if rcols[i].dtype not in _INT_KINDS:
-                return None
-        kdc_rhs, krcols = self._reconcile_dict_keys(runtime, dc_lhs, dc_rhs,
-                                                    lhs_on, rhs_on)
-        ranges = []
-        for li, ri in zip(lhs_on, rhs_on):
-            ranges.append(keys.joint_range(runtime, lcols[li], krcols[ri]))
-
-        if fprobe is not None:
-            swap = fprobe == "r"
-        elif fbuild is not None:
-            swap = fbuild == "l"
-        else:
-            swap = join_type == "right" or (
-                join_type == "inner"
-                and dc_lhs.table.num_rows < kdc_rhs.table.num_rows)
-        if swap:
-            probe_kdc, build_kdc = kdc_rhs, dc_lhs
-            probe_on, build_on = rhs_on, lhs_on
-            ktype = rt.JOIN_LEFT if join_type == "right" else rt.JOIN_INNER
-        else:
-            probe_kdc, build_kdc = dc_lhs, kdc_rhs
-            probe_on, build_on = lhs_on, rhs_on
-            ktype = {
-                "inner": rt.JOIN_INNER, "left": rt.JOIN_LEFT,
-                "leftanti": rt.JOIN_LEFTANTI,
-            }[join_type]
-
-        fp_cols = fp_keys = None
-        if pending is not None:
-            fp_cols = list(pending.prog_cols)
-            fp_keys = []
-            pk = probe_kdc.backend_cols()
-            for pi, (mn, rng) in zip(probe_on, ranges):
-                ci = next((k for k, c in enumerate(fp_cols) if c is pk[pi]),
-                          None)
-                if ci is None:
-                    fp_cols.append(pk[pi])
-                    ci = len(fp_cols) - 1
-                fp_keys.append((ci, mn, rng, False))
-        fb_cols = list(pending_b.prog_cols) if pending_b is not None else []
-        fb_keys = []
-        bk = build_kdc.backend_cols()
-        space = 1
-        for bi, (mn, rng) in zip(build_on, ranges):
-            ci = next((k for k, c in enumerate(fb_cols) if c is bk[bi]), None)
-            if ci is None:
-                fb_cols.append(bk[bi])
-                ci = len(fb_cols) - 1
-            fb_keys.append((ci, mn, rng, False))
-            space *= rng
-        return SimpleNamespace(
-            pending=pending, dc_lhs=dc_lhs, dc_rhs=dc_rhs, swap=swap,
-            ranges=ranges, ktype=ktype, probe_kdc=probe_kdc,
-            build_kdc=build_kdc, probe_on=probe_on, build_on=build_on,
-            fp_cols=fp_cols, fp_keys=fp_keys, pending_b=pending_b,
-            fb_cols=fb_cols, fb_keys=fb_keys, fb_space=space,
-            key_rewritten=(not swap) and kdc_rhs is not dc_rhs)
-
-    def _equi_join_fused(self, runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                         join_type, combined, mat_idx, cc_lhs, cc_rhs,
-                         fprobe=None, table=None, fbuild=None,
-                         build_cols=True):
-        """Equi join with fused emit+materialization (dsx_hash_probe_cols):
-        the probe's emit pass writes the output columns directly. Returns
-        ({combined_idx: DeviceColumn}, n_out) or (None, 0) on unsupported
-        shapes (caller falls back to the pair path).
-
-        fprobe "l"/"r": that side is a pending DeferredFilter and the probe
-        side of an INNER join — keys, ranges and sources then come from its
-        UNFILTERED base columns and the predicate runs inside the probe
-        (dsx_filter_probe_cols). The ranges are the base columns' cached
-        stats either way (_stats_src), so codes and table layout do not
-        change.
-
-        fbuild "l"/"r": that side is a pending DeferredFilter and the BUILD
-        side of an INNER join (_fbuild_for). The table is built straight
-        from its unfiltered base columns with the predicate inside the build
-        (dsx_hash_build_cols), so its row ids index the base columns and
-        the build-side sources below are the base columns too, for the
-        fused probe and for the duplicate-key fallback alike. A
-        materialized build side takes the same entry with an empty
-        predicate; physical/filter_build.py lists what declines."""
-        if fbuild is not None and table is not None:
-            # cannot happen: a group-join attempt materializes its build side
-            runtime.hash_table_free(table)
-            table = None
-        given = {"l": dc_lhs, "r": dc_rhs}
-        S = self._fused_setup(runtime, dc_lhs, dc_rhs, lhs_on, rhs_on,
-                              join_type, fprobe, fbuild)
-        pending = S.pending if S is not None else None
-        if table is not None and (pending is None
-                                  or len(S.fp_cols) > rt.MAX_COLS):
-            # cannot happen: the table's builder went through the same setup
-            runtime.hash_table_free(table)
-            table = None
-        if S is None:
-            return None, 0  # float keys: pair path densifies them
-        pending, dc_lhs, dc_rhs = S.pending, S.dc_lhs, S.dc_rhs
-        if S.fp_cols is not None and len(S.fp_cols) > rt.MAX_COLS:
-            # 16 program + key columns at most, else filter first
-            given[fprobe] = DataContainer(pending.table,
-                                          pending.column_container)
-            return self._equi_join_fused(
-                runtime, given["l"], given["r"], lhs_on, rhs_on, join_type,
-                combined, mat_idx, cc_lhs, cc_rhs, fbuild=fbuild)
-        fbv = self._fb_verdict(
-            join_type, fprobe, "l" in (fprobe, fbuild),
-            "r" in (fprobe, fbuild), dc_lhs.table.num_rows,
-            dc_rhs.table.num_rows, key_rewritten=S.key_rewritten,
-            n_cols=len(S.fb_cols))
-        if fbuild is not None and not fbv:
-            # the build side runs its filter after all: the old path
-            given[fbuild] = DataContainer(S.pending_b.table,
-                                          S.pending_b.column_container)
-            return self._equi_join_fused(
-                runtime, given["l"], given["r"], lhs_on, rhs_on, join_type,
-                combined, mat_idx, cc_lhs, cc_rhs, fprobe=fprobe,
-                build_cols=False)
-        # a WHERE on the build side that could not stay pending has run by
-        # now; its table is built the old way, from the compacted columns
-        fb_side = "l" if S.swap else "r"
-        use_cols = (build_cols and bool(fbv) and not (
-            fbuild is None and isinstance(given[fb_side], DeferredFilter)))
-        swap, ranges, ktype = S.swap, S.ranges, S.ktype
-        probe_kdc, build_kdc = S.probe_kdc, S.build_kdc
-        probe_on, build_on = S.probe_on, S.build_on
-        fp_cols, fp_keys = S.fp_cols, S.fp_keys
-
-        # assemble per-side materialization lists (sources: ORIGINAL tables)
-        probe_is_l = not swap
-        p_items, b_items = [], []
-        for i in mat_idx:
-            side, frontend = combined[i]
-            if side == "l":
-                col = dc_lhs.table.col(
-                    cc_lhs.get_backend_by_frontend_name(frontend))
-            else:
-                col = dc_rhs.table.col(
-                    cc_rhs.get_backend_by_frontend_name(frontend))
-            on_probe = (side == "l") == probe_is_l
-            (p_items if on_probe else b_items).append((i, col))
-        # only the fused filter-probe reads the key-membership filter; a
-        # table handed in (a declined group-join's) is that same build
-        if table is None and use_cols:
-            table = runtime.hash_build_cols(
-                runtime.make_prog(S.pending_b.prog)
-                if S.pending_b is not None else None,
-                S.fb_cols, S.fb_keys, build_kdc.table.num_rows,
-                code_max=S.fb_space - 1, key_filter=pending is not None)
-        elif table is None:
-            bcodes, bval, bkeep, space = self._key_codes(
-                runtime, build_kdc, build_on, ranges)
-            table = runtime.hash_build(bcodes, bval, code_max=space - 1,
-                                       key_filter=pending is not None)
-        try:
-            res = None
-            if pending is not None:
-                res = runtime.filter_probe_cols(
-                    table, runtime.make_prog(pending.prog), fp_cols, fp_keys,
-                    pending.max_rows, [c for _, c in p_items],
-                    [c for _, c in b_items])
-                if res is None:
-                    # duplicate build keys: run the filter after all and
-                    # probe the same table the two-pass way
-                    dc_l2, dc_r2 = self._materialized(fprobe, pending,
-                                                      dc_lhs, dc_rhs)
-                    if swap:
-                        probe_kdc, _ = self._reconcile_dict_keys(
-                            runtime, dc_l2, dc_r2, lhs_on, rhs_on)
-                    else:
-                        probe_kdc = dc_l2
-                    src_dc, src_cc = (dc_r2, cc_rhs) if swap \
-                        else (dc_l2, cc_lhs)
-                    p_items = [
-                        (i, src_dc.table.col(
-                            src_cc.get_backend_by_frontend_name(
-                                combined[i][1])))
-                        for i, _ in p_items]
-            if res is None:
-                pcodes, pval, pkeep, _ = self._key_codes(
-                    runtime, probe_kdc, probe_on, ranges)
-                res = runtime.hash_probe_cols(
-                    table, pcodes, ktype, pval,
-                    [c for _, c in p_items], [c for _, c in b_items],
-                    force_build_validity=(ktype == rt.JOIN_LEFT))
-            cols_out, n_out = res
-        finally:
-            runtime.hash_table_free(table)
-        gathered = {}
-        for (i, src), col in zip(p_items + b_items, cols_out):
-            if getattr(src, "dictionary", None) is not None:
-                col.dictionary = src.dictionary
-            col._stats_src = src
-            gathered[i] = col
-        return gathered, n_out
-
-    @staticmethod
-    def _materialized(fprobe, pending, dc_lhs, dc_rhs):
-        """(dc_lhs, dc_rhs) with the pending side's filter run."""
-        done = DataContainer(pending.table, pending.column_container)
-        return (done, dc_rhs) if fprobe == "l" else (dc_lhs, done)
-
-    def _cross_join(self, runtime, dc_lhs, dc_rhs, join_type):
-        # reference join.py:133-140 (merge on constant); tiny-only guard
-        n_l = dc_lhs.table.num_rows
-        n_r = dc_rhs.table.num_rows
-        if n_l * n_r > 50_000_000:
-            raise NotImplementedError(
-                f"cross join of {n_l}x{n_r} rows is unreasonable "
-                "(reference warns ResourceWarning too, join.py:141-145)")
-        p = np.repeat(np.arange(n_l, dtype=np.uint32), n_r)
-        b = np.tile(np.arange(n_r, dtype=np.uint32), n_l)
-        probe_sel = runtime.upload_column(p, dtype=rt.I32)
-        build_sel = runtime.upload_column(b, dtype=rt.I32)
-        return (probe_sel, build_sel), int(n_l * n_r)
-
-    def _split_join_condition(self, condition, n_lhs_cols):
-        """reference join.py:250-322 — equi-keys + residual split."""
-        rex_type = str(condition.getRexType())
-        if rex_type in ("RexType.Literal", "RexType.Reference"):
-            return [], [], [condition]
-        if rex_type != "RexType.Call":
-            raise NotImplementedError("Can not understand join condition.")
-        lhs_on, rhs_on, residual = [], [], []
-        try:
-            lhs_on, rhs_on, residual = self._extract_lhs_rhs(condition,
-                                                             n_lhs_cols)
-        except AssertionError:
-            residual = [condition]
-        if lhs_on and rhs_on:
-            return lhs_on, rhs_on, residual
-        return [], [], [condition]
-
-    def _extract_lhs_rhs(self, rex, n_lhs_cols):
-        # reference join.py:274-322
-        assert str(rex.getRexType()) == "RexType.Call"
-        op = str(rex.getOperatorName())
-        assert op in ("=", "AND")
-        operands = rex.getOperands()
-        assert len(operands) == 2
-        if op == "=":
-            a, b = operands
-            if str(a.getRexType()) == "RexType.Reference" and \
-                    str(b.getRexType()) == "RexType.Reference":
-                ai, bi = a.getIndex(), b.getIndex()
-                if ai > bi:
-                    ai, bi = bi, ai
-                assert ai < n_lhs_cols <= bi, "both refs on one side"
-                return [ai], [bi - n_lhs_cols], []
-            raise AssertionError("Invalid join condition")
-        lhs_idx, rhs_idx, residual = [], [], []
-        for operand in operands:
-            try:
-                li, ri, res = self._extract_lhs_rhs(operand, n_lhs_cols)
-                lhs_idx.extend(li)
-                rhs_idx.extend(ri)
-                residual.extend(res)
-            except AssertionError:
-                residual.append(operand)
-        return lhs_idx, rhs_idx, residual
 
 
 # aggregates the device kernels do not carry; the reference itself runs
@@ -1846,23 +842,15 @@ class DaskAggregatePlugin(BaseRelPlugin):
             return None, None, None
         if str(base_rel.join().getJoinType()) != "INNER":
             return None, None, None
-        inputs = jp.assert_inputs(base_rel, 2, context)
-        J = jp._prepare(base_rel, *inputs)
-        fprobe = jp._fprobe_for(J)
+        # the prepared join stands for its inputs from here on
+        inputs = J = jp.prepare(base_rel,
+                                *jp.assert_inputs(base_rel, 2, context))
+        R = jp.route(J, group_join=True)  # the build side's WHERE runs first
+        fprobe = R.fprobe
         out_idx = J.out_idx
 
-        def side_cols(dc):
-            return (dc.unfiltered() if _pending_filter(dc)
-                    else dc).backend_cols()
-
-        def kd(col, side):
-            if getattr(col, "dictionary", None) is not None:
-                return ("dict", side)  # string keys: per-side codes
-            return col.dtype
-
-        lcols, rcols = side_cols(J.dc_lhs), side_cols(J.dc_rhs)
-        key_dtypes = [(kd(lcols[li], "l"), kd(rcols[ri], "r"))
-                      for li, ri in zip(J.lhs_on, J.rhs_on)]
+        key_dtypes = [(jp.key_dtype(lc, "l"), jp.key_dtype(rc, "r"))
+                      for lc, rc in zip(*jp.key_columns(J))]
         group_cols = []
         for e in group_exprs:
             pe = named[e.getIndex()][0]
@@ -1896,16 +884,11 @@ class DaskAggregatePlugin(BaseRelPlugin):
         pending = J.dc_lhs if fprobe == "l" else J.dc_rhs
         if pending.max_rows < gj.min_rows():
             return None, inputs, None
-        S = jp._fused_setup(runtime, J.dc_lhs, J.dc_rhs, J.lhs_on, J.rhs_on,
-                            "inner", fprobe)
-        if S is None:
-            return None, inputs, None
+        R = jp.settle(J, R, group_join=True)
+        S = jp.fused_setup(runtime, J, R)
 
         def src_col(ci):
-            side, frontend = J.combined[ci]
-            dc, cc = (S.dc_lhs, J.cc_lhs) if side == "l" \
-                else (S.dc_rhs, J.cc_rhs)
-            return dc.table.col(cc.get_backend_by_frontend_name(frontend))
+            return source_col(J, ci, S.dc_lhs, S.dc_rhs)
 
         # the aggregate arguments' probe columns join the predicate's and
         # the keys' in the entry's one column list
@@ -1949,22 +932,9 @@ class DaskAggregatePlugin(BaseRelPlugin):
             kcols.append(build_cols[S.build_on[i]] if kind == "key"
                          else src_col(g))
             group_meta.append((named[e.getIndex()][1], src_col(g)))
-        # the build side is materialized here (a pending one has run by now:
-        # the accumulators are sized by the table's build rows), so the
-        # build-from-columns entry takes it with an empty predicate
-        n_b = S.build_kdc.table.num_rows
-        if jp._fb_verdict("inner", fprobe, fprobe == "l", fprobe == "r",
-                          S.dc_lhs.table.num_rows, S.dc_rhs.table.num_rows,
-                          key_rewritten=S.key_rewritten,
-                          n_cols=len(S.fb_cols)):
-            table = runtime.hash_build_cols(
-                None, S.fb_cols, S.fb_keys, n_b, code_max=S.fb_space - 1,
-                key_filter=True)
-        else:
-            bcodes, bval, bkeep, space = jp._key_codes(
-                runtime, S.build_kdc, S.build_on, S.ranges)
-            table = runtime.hash_build(bcodes, bval, code_max=space - 1,
-                                       key_filter=True)
+        # the build side is materialized by now, so the build-from-columns
+        # entry takes it with an empty predicate
+        table = jp.build_table(runtime, S, R, key_filter=True)
         try:
             res = runtime.filter_probe_groupby(
                 table, runtime.make_prog(S.pending.prog), fp_cols, S.fp_keys,
