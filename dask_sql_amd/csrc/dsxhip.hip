@@ -4327,6 +4327,7 @@ void jit_cache_destroy(DsxCtx* c) {
 #include "radix_sort.inc"
 #include "window.inc"
 #include "window_rows.inc"
+#include "window_range.inc"
 #include "window_words.inc"
 #include "topk.inc"
 #include "group_join.inc"

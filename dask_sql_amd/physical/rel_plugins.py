@@ -1990,7 +1990,7 @@ def _topk(pdf, keys, k):
 class DaskWindowPlugin(BaseRelPlugin):
     """reference rel/logical/window.py:212-428 (OverOperation dispatch +
     map_on_each_group over sorted partitions). _one routes each window
-    column to one of three device paths:
+    column to one of four device paths:
 
     - unordered partition aggregates (SUM/COUNT/AVG/MIN/MAX OVER
       (PARTITION BY …)), _device_agg: fused groupby, hash join-back of the
@@ -2003,11 +2003,20 @@ class DaskWindowPlugin(BaseRelPlugin):
       over ROWS BETWEEN … AND … / ROWS k PRECEDING), _device_rows: the
       sort front half, then dsx_window_rows (LDS tile pass for narrow
       bounded frames, per-partition scans + prefix differences
-      otherwise).
+      otherwise);
+    - RANGE frames with value offsets (the same seven functions over
+      RANGE BETWEEN … AND … with numeric or INTERVAL offsets),
+      _device_range: the sort front half with peer ids, then
+      dsx_window_range (frame bounds by binary search over the sorted
+      order key, the same scans, a sparse table for MIN/MAX bounded on
+      both sides). What it declines runs on the numpy model of the same
+      SQL semantics (_host_range, physical/window_range.py), never on
+      _frame_apply, which knows row offsets only.
 
-    What these decline runs as the reference computes it, in pandas per
-    partition on the host (_host_ordered, _frame_apply; window.py:266-427
-    map_on_each_group), and the one result column is uploaded:
+    What the others decline runs as the reference computes it, in pandas
+    per partition on the host (_host_ordered, _frame_apply;
+    window.py:266-427 map_on_each_group), and the one result column is
+    uploaded:
     DSX_DISABLE_DEVWINDOW set, a key dtype that is not device-sortable, a
     single integer key spanning more than 2^62, a dictionary-encoded
     value column, OVER () aggregates, or a bounded MIN/MAX frame wider
@@ -2050,6 +2059,18 @@ class DaskWindowPlugin(BaseRelPlugin):
 
     def _one(self, runtime, cols, n, spec):
         import os as _os
+        if getattr(spec, "frame", None) is not None \
+                and spec.frame[0] == "range":
+            # RANGE frames with value offsets: dsx_window_range, or the
+            # numpy model of the same semantics. Never _frame_apply, which
+            # ignores the frame kind and would answer with row semantics:
+            # tested before every route that ends in _host_ordered. An
+            # explicit NULLS FIRST with the word front half off is declined
+            # by _device_sort_keys and honoured by the host model
+            col = self._device_range(runtime, cols, n, spec)
+            if col is not None:
+                return col
+            return self._host_range(runtime, cols, n, spec)
         if any(nf is True for nf in getattr(spec, "order_nf", [])) \
                 and _os.environ.get("DSX_DISABLE_WINWORDS", "0") == "1":
             # explicit NULLS FIRST on a window order key is sorted by the
@@ -2094,6 +2115,10 @@ class DaskWindowPlugin(BaseRelPlugin):
         (window.py:145-198)."""
         import pandas as pd
         fk, lo, hi = spec.frame
+        if fk != "rows":
+            # row offsets only: a RANGE frame answered here would be wrong
+            # without an error (_one sends those to _host_range)
+            raise RexCompileError(f"{fk.upper()} frame on the ROWS host path")
         f = spec.func
         src = "v" if spec.arg_idx is not None else "_one_"
         if src == "_one_":
@@ -2369,6 +2394,118 @@ class DaskWindowPlugin(BaseRelPlugin):
         col = runtime.window_rows(perm, n, ps, func, v_col, lo_off, hi_off,
                                   out_dtype, want_valid)
         col._keep_alive = (perm, ps, v_col)
+        return col
+
+    @staticmethod
+    def _range_out(spec, v_col, lo, hi):
+        """(kind, with_validity) of a RANGE-framed column, shared by the
+        device and host routes so both produce the same dtype."""
+        from dask_sql_amd.physical import window_range as wrg
+        is_big = spec.out_type is not None and \
+            spec.out_type.getSqlType() == "BIGINT"
+        return wrg.range_out_dtype(
+            spec.func, lo, hi, is_big,
+            v_col is not None and bool(v_col.validity))
+
+    def _device_range(self, runtime, cols, n, spec):
+        """Device RANGE frames with value offsets (dsx_window_range): the
+        sort front half with peer ids, then per-row frame bounds by binary
+        search over the sorted order key, the per-partition scans and, for
+        a MIN/MAX bounded on both sides, the sparse table. Returns None →
+        window_range.range_frames_host: DSX_DISABLE_DEVWINDOW, an empty
+        table, a dictionary-encoded value column, a key the device does not
+        sort, OVER () without any key, or a table above
+        DSX_WIN_RANGE_RMQ_MAX_BYTES."""
+        import os as _os
+        from dask_sql_amd.physical import window_range as wrg
+        if _os.environ.get("DSX_DISABLE_DEVWINDOW") or n == 0:
+            return None
+        func = spec.func
+        if func not in runtime.WIN_ROWS_FUNCS:
+            return None
+        v_col = cols[spec.arg_idx] if spec.arg_idx is not None else None
+        if v_col is None and func != "count":
+            return None
+        if v_col is not None and getattr(v_col, "dictionary",
+                                         None) is not None:
+            return None  # string payload: host
+        lo, hi = wrg.frame_bounds(spec.frame)
+        k_col, desc = None, False
+        if wrg.OFFSET in (lo.kind, hi.kind):
+            ki, desc = spec.order_idx[0]
+            k_col = cols[ki]
+            if k_col.dtype not in (rt.I64, rt.I32, rt.I8, rt.F64, rt.F32) \
+                    or getattr(k_col, "dictionary", None) is not None:
+                return None
+        if wrg.needs_rmq(func, lo, hi) \
+                and wrg.rmq_table_bytes(n) > wrg.rmq_max_bytes():
+            # the library would answer -7; decline before the sort
+            return None
+        sort = self._device_sort_keys(runtime, cols, n, spec, need_full=True)
+        if sort is None:
+            return None
+        perm, ps, fs = sort
+        kind, want_valid = self._range_out(spec, v_col, lo, hi)
+        out_dtype = {"i64": rt.I64, "f64": rt.F64}.get(kind)
+        if out_dtype is None:
+            out_dtype = v_col.dtype
+        col = runtime.window_range(perm, n, ps, fs, func, v_col, k_col, desc,
+                                   lo, hi, out_dtype, want_valid)
+        if col is None:
+            return None
+        col._keep_alive = (perm, ps, fs, v_col, k_col)
+        return col
+
+    def _host_range(self, runtime, cols, n, spec):
+        """RANGE frames on the host: download the key and value columns
+        like _host_ordered and run the numpy model of the same semantics
+        (window_range.range_frames_host)."""
+        from dask_sql_amd.physical import window_range as wrg
+
+        def key_of(i):
+            arr, valid = cols[i].to_numpy()
+            dic = getattr(cols[i], "dictionary", None)
+            if dic is not None:
+                # dictionary codes → ranks in string order
+                order = np.argsort(np.asarray(list(dic), dtype=object),
+                                   kind="mergesort")
+                rank = np.empty(len(order), dtype=np.int64)
+                rank[order] = np.arange(len(order))
+                ok = valid if valid is not None else \
+                    np.ones(len(arr), dtype=bool)
+                arr = np.where(ok, rank[np.where(ok, arr, 0)], 0)
+            return arr, valid
+
+        func = spec.func
+        if func not in wrg.RANGE_FUNCS:
+            raise RexCompileError(
+                f"window function {func} with a RANGE frame")
+        v_col = cols[spec.arg_idx] if spec.arg_idx is not None else None
+        if v_col is None and func != "count":
+            raise RexCompileError(f"{func} with a RANGE frame needs an "
+                                  "operand")
+        dic = getattr(v_col, "dictionary", None) if v_col is not None \
+            else None
+        if dic is not None and func not in wrg.RANGE_POSITIONAL:
+            raise RexCompileError(
+                f"{func} over a string column with a RANGE frame")
+        lo, hi = wrg.frame_bounds(spec.frame)
+        pid = wrg.dense_ids([key_of(i) for i in spec.part_idx]) \
+            if spec.part_idx else np.zeros(n, dtype=np.int64)
+        nfs = list(getattr(spec, "order_nf", [])) or \
+            [None] * len(spec.order_idx)
+        order = [key_of(i) + (bool(desc), nf is True)
+                 for (i, desc), nf in zip(spec.order_idx, nfs)]
+        value, value_valid = v_col.to_numpy() if v_col is not None \
+            else (None, None)
+        kind, _want_valid = self._range_out(spec, v_col, lo, hi)
+        out, ok = wrg.range_frames_host(func, pid, order, value, value_valid,
+                                        lo, hi, kind)
+        col = runtime.upload_column(
+            out, validity=ok,
+            dtype=v_col.dtype if kind == "value" else None)
+        if dic is not None:
+            col.dictionary = dic
         return col
 
     def _device_agg(self, runtime, cols, n, spec):

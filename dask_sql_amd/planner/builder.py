@@ -1298,9 +1298,16 @@ class Builder:
             if frame is not None:
                 fk, lo, hi = frame
                 if fk == "range":
-                    raise NotImplementedError(
-                        "RANGE frames with offsets (ROWS frames and the "
-                        "default RANGE frame are supported)")
+                    from dask_sql_amd.planner import range_frame as wrg
+                    if func not in wrg.RANGE_FUNCS:
+                        raise NotImplementedError(
+                            "RANGE frames with offsets (ROWS frames and the "
+                            "default RANGE frame are supported)")
+                    # validated here, every offset resolved to the order
+                    # key's unit (days, nanoseconds, the key's own number)
+                    frame = wrg.resolve_range_frame(
+                        frame, [pre_fields[i].getType().getSqlType()
+                                for i, _desc in order_idx])
             name = f"w{len(specs)}__{func}"
             spec = WindowSpec(func, arg_idx, part_idx, order_idx,
                               name, SqlType(ty), offset=offset,

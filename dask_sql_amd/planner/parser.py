@@ -938,6 +938,29 @@ class Parser:
                     if self._accept_word("CURRENT"):
                         self._expect_word("ROW")
                         return ("current", 0)
+                    if fk == "RANGE":
+                        # a value offset: integer, decimal or INTERVAL
+                        # literal; the builder resolves it to the order
+                        # key's unit
+                        neg = bool(self.accept_op("-"))
+                        t = self.peek()
+                        if t == ("kw", "INTERVAL"):
+                            k = self.primary()
+                        elif t[0] == "num":
+                            self.next()
+                            txt = t[1]
+                            k = float(txt) if "." in txt \
+                                or "e" in txt.lower() else int(txt)
+                        else:
+                            raise ValueError(f"bad frame bound {t}")
+                        if neg or (not isinstance(k, tuple) and k < 0) \
+                                or (isinstance(k, tuple) and k[1] < 0):
+                            raise ValueError(
+                                "a RANGE frame offset must not be negative")
+                        if self._accept_word("PRECEDING"):
+                            return ("preceding", k)
+                        self._expect_word("FOLLOWING")
+                        return ("following", k)
                     t = self.next()
                     if t[0] != "num":
                         raise ValueError(f"bad frame bound {t}")

@@ -90,6 +90,11 @@ class _AggSpec(ct.Structure):
     ]
 
 
+class _WinBound(ct.Structure):
+    _fields_ = [("kind", ct.c_int32), ("ival", ct.c_int64),
+                ("fval", ct.c_double)]
+
+
 class _GbFinishCall(ct.Structure):
     _fields_ = [("kind", ct.c_int32), ("agg", ct.c_int32)]
 
@@ -915,6 +920,42 @@ class Runtime:
                 ct.c_int(1 if want_valid else 0)),
             "dsx_window_rows",
         )
+        return DeviceColumn(self, d.value, vv.value or None, n, out_dtype,
+                            owner=True)
+
+    def window_range(self, perm, n, pcode_sorted, fcode_sorted, func, v_col,
+                     key_col, desc, lo, hi, out_dtype, want_valid):
+        """Device RANGE frame with value offsets (dsx_window_range). lo / hi
+        are ``(kind, value)`` with kind 0 unbounded, 1 current row, 2 signed
+        offset in the order key's unit; key_col (original row order) may be
+        None when no bound is an offset. None when the library declines the
+        frame (-7: the MIN/MAX table would exceed
+        DSX_WIN_RANGE_RMQ_MAX_BYTES)."""
+        d = ct.c_void_p()
+        vv = ct.c_void_p()
+        vstruct = v_col.c_struct() if v_col is not None else None
+        kstruct = key_col.c_struct() if key_col is not None else None
+
+        def bound(b):
+            kind, value = b
+            if kind != 2:
+                return _WinBound(kind, 0, 0.0)
+            return _WinBound(kind, int(value) if not isinstance(value, float)
+                             else 0, float(value))
+
+        blo, bhi = bound(lo), bound(hi)
+        rc = self.lib.dsx_window_range(
+            self.ctx, ct.c_void_p(perm.data), ct.c_int64(n),
+            ct.c_void_p(pcode_sorted.data), ct.c_void_p(fcode_sorted.data),
+            ct.c_int(self.WIN_ROWS_FUNCS[func]),
+            ct.byref(vstruct) if vstruct is not None else None,
+            ct.byref(kstruct) if kstruct is not None else None,
+            ct.c_int(1 if desc else 0), ct.byref(blo), ct.byref(bhi),
+            ct.c_int(out_dtype), ct.byref(d), ct.byref(vv),
+            ct.c_int(1 if want_valid else 0))
+        if rc == -7:
+            return None
+        _check(self.lib, rc, "dsx_window_range")
         return DeviceColumn(self, d.value, vv.value or None, n, out_dtype,
                             owner=True)
 

@@ -453,6 +453,54 @@ int dsx_window_rows(DsxCtx* ctx, const uint32_t* perm, int64_t n,
                     int out_dtype, void** out_data, uint8_t** out_valid,
                     int want_valid);
 
+/* One bound of a RANGE frame: the partition edge, the edge of the current
+ * row's peer group, or a signed offset in the order key's unit (PRECEDING
+ * negative) — ival for integer, date and timestamp keys, fval for float
+ * keys. */
+enum DsxWinBoundKind {
+  DSX_WIN_BOUND_UNBOUNDED = 0,
+  DSX_WIN_BOUND_CURRENT = 1,
+  DSX_WIN_BOUND_OFFSET = 2,
+};
+typedef struct DsxWinBound {
+  int32_t kind; /* DsxWinBoundKind */
+  int64_t ival;
+  double fval;
+} DsxWinBound;
+
+/* Device RANGE frames with value offsets (SQL standard semantics, as sqlite
+ * computes them). Inputs follow dsx_window_rows, plus the sorted peer codes
+ * (partition + order keys; adjacent values differ exactly at a peer-group
+ * boundary), the order-key column in ORIGINAL row order (I64/I32/I8 or
+ * F64/F32; may be NULL when no bound is an OFFSET), its direction, and the
+ * two bounds. With d = +1 (ASC) / -1 (DESC), a row of non-NULL key k frames
+ * the non-NULL-key rows j of its partition with lo <= d * (key[j] - k) <=
+ * hi; k + offset saturates at the int64 limits (a target whose exact
+ * value lies beyond the limit no key can reach admits no row, also not a
+ * key AT the limit); NaN keys count as NULL. A
+ * NULL-key row's offset side ends at the edge of its peer group (the NULL
+ * block). CURRENT is the peer group's first / last row, UNBOUNDED the
+ * partition edge. An EMPTY frame is NULL for every function except COUNT,
+ * which is 0. func as for dsx_window_rows:
+ *  - SUM/COUNT/AVG: forward per-partition scan + prefix difference;
+ *  - MIN/MAX with an unbounded side: forward / reverse scan lookup;
+ *  - MIN/MAX with both sides bounded: a sparse table over 64-row blocks
+ *    (8 * ceil(n / 64) * levels bytes from the pool, levels =
+ *    floor(log2(blocks)) + 1). Above DSX_WIN_RANGE_RMQ_MAX_BYTES
+ *    (environment, read per call, default 1 GiB) the call returns -7 and
+ *    the caller keeps the frame on the host;
+ *  - FIRST/LAST: positional bit copy in the value dtype.
+ * n <= 2^32 - 1. Results land in original row order. On failure nothing
+ * stays allocated and *out_data / *out_valid are NULL. */
+int dsx_window_range(DsxCtx* ctx, const uint32_t* perm, int64_t n,
+                     const uint64_t* pcode_sorted,
+                     const uint64_t* fcode_sorted, int func,
+                     const DsxColumn* value_or_null,
+                     const DsxColumn* key_or_null, int desc,
+                     const DsxWinBound* lo, const DsxWinBound* hi,
+                     int out_dtype, void** out_data, uint8_t** out_valid,
+                     int want_valid);
+
 /* Boundary marks of ONE order word over a sorted row sequence — the window
  * front half for keys that do not pack into one code (float keys, more than
  * DSX_MAX_KEYS keys, key spaces above 2^62; reference rel/logical/
